@@ -12,9 +12,18 @@ utils.py:98; here one fused flag reduction whose last block hands the words to t
 so `value` is the streaming, validation-inclusive rate; the same step on pre-built (already validated, flag-cached) objects
 is reported as `value_cached_flow_objects`.  The metric is Mpix/s = global batch * H * W / t_step ("warped+composed").
 
-Timing: `--blocks` R blocks (default max(5, 500 / steps)) of EXACTLY `--steps` K steps each, every block bracketed by a
-barrier + `torch.cuda.synchronize()` on both sides (MAX over the ranks per block); `value` / `ms_per_step` are the MEDIAN
-block, `timing` carries min / median / max.  `roofline` is the dominant kernel (Flow.apply 't'), its average launch duration
+Timing: `--blocks` R blocks of EXACTLY `--steps` K steps each, every block bracketed by a barrier + `torch.cuda.synchronize()`
+on both sides (MAX over the ranks per block); `value` / `ms_per_step` are the MEDIAN block, `timing` carries min / median /
+max.  A plain run times ONE block by default (K timed steps in all) and prints only the headline: set-up, `--warmup` W
+steps, the K timed steps, `--dump-outputs`, the line.  Only `--full` (there R defaults to max(5, 500 / steps)) measures
+`value_cached_flow_objects`, `kernels`, `roofline`, `weak_scaling`, `strong_scaling_probe`, `secondary` and `cpu_baseline`.
+
+`--dump-outputs DIR` writes what the last timed step returned -- `warped.npy`, `valid.npy` (Flow.apply) and
+`combined_vecs.npy`, `combined_mask.npy` (combine_with) -- as float32 (masks as 0 / 1).  Those of more than DUMP_ELEMS values
+are written as a fixed sample of them (seeded, sorted flat positions).  The inputs are seeded, so two runs with the same
+arguments, e.g. of two builds, compare output for output.  Under N > 1 rank 0 writes its own shard.
+
+`roofline` is the dominant kernel (Flow.apply 't'), its average launch duration
 from HIP events on the launch stream over >= 100 launches; `traffic` comes from an earlier rocprofv3 --pmc pass of this
 command (`traffic_source` says which).  `secondary` (N = 1): the other single-GPU configurations of BASELINE.json --
 configs[1] B = 1 apply 't', configs[2] B = 16 apply 's', configs[4] per GPU (B = 16 4K fp16: switch_ref + mode 1) -- each with
@@ -22,11 +31,12 @@ ms, algorithmic B/px and the fraction of 8 TB/s.
 
     --scaling weak   (default) B = --batch (64) PER GPU: every rank owns its own shard, no data-path collective
     --scaling strong           --batch (64) is the GLOBAL batch (BASELINE.json configs[3]): 64 / 32 / 16 / 8 per GPU at 1 / 2 / 4 / 8
-At N = 1 the line also carries `strong_scaling_probe`: the same step at the 8 elements per GPU that config 4 leaves each
+At N = 1 a --full line also carries `strong_scaling_probe`: the same step at the 8 elements per GPU that config 4 leaves each
 of 8 GPUs, with the per-step host overhead (wall time minus HIP-event kernel time) -- what bounds strong scaling.
 Under torch.distributed.run the process group (backend "nccl" = RCCL) is initialised at every N, also N = 1.
 
-    python bench.py                       # 1 GPU, defaults finish in a couple of minutes
+    python bench.py                       # 1 GPU, the headline only: seconds
+    python bench.py --full                # everything above: a couple of minutes
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -45,6 +55,7 @@ import torch.nn.functional as F  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0                    # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 BYTES_APPLY, BYTES_COMBINE = 35, 27      # algorithmic B/px
+DUMP_ELEMS = 1 << 21                     # --dump-outputs: values per array at most (8 MiB of float32; 32 MiB for the four)
 
 
 def smooth_flow(n, h, w, sigma, seed, device):
@@ -72,6 +83,20 @@ def make_inputs(n, h, w, device, seed):
     m1, m2 = hole_mask(n, h, w, device), hole_mask(n, h, w, device).flip(2)
     tm = hole_mask(n, h, w, device).flip(1)
     return f1, f2, img, m1, m2, tm
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (bool masks as 0 / 1).  An array of more than DUMP_ELEMS
+    values is written as DUMP_ELEMS of them, flat, at positions drawn by a generator of fixed seed and sorted: the same
+    positions in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() > DUMP_ELEMS:
+            g = torch.Generator(device='cpu').manual_seed(4242)
+            idx = torch.randint(t.numel(), (DUMP_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def _cpu_model():
@@ -182,6 +207,33 @@ def _loop_ms(fn, iters, blocks=5, warm=10):
     return sum(t) / blocks, t[blocks // 2], t[0]
 
 
+def stream_probes(dev):
+    """-> (device-copy GB/s, read-mostly stream GB/s) measured here, the `roofline`'s same-box reference points."""
+    # measured device-copy ceiling (SURVEY.md 8d): a 1 GiB fp32 copy on the same stream, read + write bytes / time
+    a = torch.empty(1 << 28, dtype=torch.float32, device=dev)
+    b = torch.empty_like(a)
+    b.copy_(a)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(5):
+        b.copy_(a)
+    e1.record()
+    torch.cuda.synchronize()
+    copy_gbs = 5 * 2 * a.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+    # a stream with the apply kernel's byte mix -- 22 bytes read for 13 written (flow 8 + image 12 + two masks | image 12 + mask 1) --
+    # as plain torch elementwise work: out[13 parts] = f(in[22 parts]) over 1 GiB; what a streaming kernel of this mix reaches here
+    parts = a.numel() // 22
+    src22, dst13 = a[:22 * parts].view(22, parts), b[:13 * parts].view(13, parts)
+    torch.add(src22[:13], src22[9:22], out=dst13)                       # (reads all 22 rows -- rows 9..12 twice, from cache -- writes 13)
+    e0.record()
+    for _ in range(5):
+        torch.add(src22[:13], src22[9:22], out=dst13)
+    e1.record()
+    torch.cuda.synchronize()
+    mix_gbs = 5 * 35 * parts * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+    return copy_gbs, mix_gbs
+
+
 def secondary_lines(ofl, dev):
     """The other single-GPU configurations of BASELINE.json, timed the same way (HIP events round the whole operation, inputs
     resident, objects built inside the timed call where the config says so): ms, algorithmic B/px and the
@@ -261,7 +313,7 @@ def _sharded_child(route, steps):
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=port,
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--batch", "8", "--steps", str(steps), "--warmup", "5", "--blocks", "5",
-           "--no-secondary", "--no-cpu-baseline", "--no-probe", "--force-collectives", "--flag-route", route]
+           "--full", "--no-secondary", "--no-cpu-baseline", "--no-probe", "--force-collectives", "--flag-route", route]
     try:
         res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
         line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1]
@@ -270,10 +322,10 @@ def _sharded_child(route, steps):
         return None
 
 
-def _self_launch(n):
+def _self_launch(n, extra=()):
     """`python bench.py --gpus N` (N > 1) outside torch.distributed.run: run `python -m torch.distributed.run --nnodes=1
-    --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same arguments>` as a child, relay the JSON line rank 0
-    prints, return the child's exit code (with its stderr on failure).  Nothing here touches the GPU."""
+    --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <same arguments> <extra>` as a child, relay the JSON line
+    rank 0 prints, return the child's exit code (with its stderr on failure).  Nothing here touches the GPU."""
     import socket
     import subprocess
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sock:
@@ -283,7 +335,7 @@ def _self_launch(n):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-           "--master-port", port, os.path.abspath(__file__)] + sys.argv[1:]
+           "--master-port", port, os.path.abspath(__file__)] + sys.argv[1:] + list(extra)
     res = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=ROOT)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     if res.returncode != 0 or not lines:
@@ -297,10 +349,15 @@ def _self_launch(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps per block (a plain run times one block: --steps in all)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--blocks", type=int, default=0,
-                    help="timed blocks of EXACTLY --steps steps each (0: max(5, 500 / steps)); `value` is the median block")
+                    help="timed blocks of EXACTLY --steps steps each (0: 1, under --full max(5, 500 / steps)); `value` is the median block")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: cached objects, per-launch kernel times, roofline, weak "
+                         "scaling, the strong-scaling probe, secondary configurations, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32; a fixed sample of larger arrays)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary lines (BASELINE configs 2, 3, 5)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default=None,
                     help="default: strong (a global batch of --batch, BASELINE configs[3]) at N > 1, weak at N = 1 (the same job there)")
@@ -325,14 +382,19 @@ def main():
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch of the dominant kernel from a separate rocprofv3 --pmc pass")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if (args.gpus > 1 or args.self_launch) and "RANK" not in os.environ:
         # plain `python bench.py --gpus N`: start the N ranks ourselves, as FRESH child processes, before this process has made
-        # any GPU call (a process that has touched the GPU must never be replaced), and relay rank 0's line
-        sys.exit(_self_launch(args.gpus))
+        # any GPU call (a process that has touched the GPU must never be replaced), and relay rank 0's line; the ranks run in
+        # the repository root, so the dump directory goes to them as an absolute path
+        sys.exit(_self_launch(args.gpus, ["--dump-outputs", args.dump_outputs] if args.dump_outputs else []))
     if world != args.gpus:
         sys.exit("bench.py --gpus %d is running under WORLD_SIZE=%d: launch it with torch.distributed.run --nproc-per-node %d, "
                  "or without RANK / WORLD_SIZE in the environment (it then starts its ranks itself)" % (args.gpus, world, args.gpus))
@@ -371,10 +433,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(nb, steps, warmup, seed, blocks):
+    def measure(nb, steps, warmup, seed, blocks, full=True):
         """`blocks` timed blocks of EXACTLY `steps` steps each (barrier + synchronize on both sides of every block), validation
-        inclusive and on cached objects; then HIP events round every launch of max(steps, 100) more steps.
-        -> per-block seconds (both flavours) and the per-launch kernel times in ms"""
+        inclusive; with `full` the same on cached objects, then HIP events round every launch of max(steps, 100) more steps.
+        -> per-block seconds, the arrays the last timed step returned, and with `full` the cached flavour's per-block seconds
+        and the per-launch kernel times in ms"""
         f1, f2, img, m1, m2, tm = make_inputs(nb, h, w, dev, seed=seed)
         bcast_ev = []
         if args.shared_image:
@@ -398,8 +461,8 @@ def main():
 
         def step_streaming():
             a, b = ofl.Flow(f1, 't', m1), ofl.Flow(f2, 't', m2)        # validation: one fused flag reduction + read-back each
-            b.apply(img, target_mask=tm, return_valid_area=True)
-            a.combine_with(b, 3)
+            warped, valid = b.apply(img, target_mask=tm, return_valid_area=True)
+            return warped, valid, a.combine_with(b, 3)
         for _ in range(warmup):
             step_streaming()
         stream_s = []
@@ -409,14 +472,22 @@ def main():
             assert torch.equal(img, own_img) and torch.equal(tm, own_tm), "broadcast_operand did not deliver rank 0's operand"
         ranks_seen = 1
         for _ in range(blocks):
+            last = None                                                 # (the previous block's outputs go outside the timed region)
             barrier()
             t0 = time.perf_counter()
             share()                                                     # (inside the timed region, once per block)
-            for _ in range(steps):                                      # EXACTLY `steps` timed steps per block
+            for _ in range(steps - 1):                                  # EXACTLY `steps` timed steps per block
                 step_streaming()
+            last = step_streaming()
             ranks_seen = dist.get_world_size() if dist.is_initialized() else 1      # the communicator as seen INSIDE the timed region
             barrier()
             stream_s.append(time.perf_counter() - t0)
+        warped, valid, f3 = last
+        bms = sorted(e0.elapsed_time(e1) for e0, e1 in bcast_ev[1:]) if len(bcast_ev) > 1 else []
+        res = {"stream_s": stream_s, "rccl_ranks": ranks_seen, "broadcast_ms": (bms[len(bms) // 2] if bms else None),
+               "outputs": {"warped": warped, "valid": valid, "combined_vecs": f3.vecs, "combined_mask": f3.mask}}
+        if not full:
+            return res
         # the same step on pre-built objects (validation cached per tensor version)
         flow1, flow2 = ofl.Flow(f1, 't', m1), ofl.Flow(f2, 't', m2)
 
@@ -446,31 +517,35 @@ def main():
         barrier()
         ta = sorted(e[0].elapsed_time(e[1]) for e in ev)
         tc = sorted(e[1].elapsed_time(e[2]) for e in ev)
-        bms = sorted(e0.elapsed_time(e1) for e0, e1 in bcast_ev[1:]) if len(bcast_ev) > 1 else []
         flow2.apply(img, target_mask=tm, return_valid_area=True)
         kernel_apply = _native.last_kernel_name()                  # the instantiation the launcher picked for THIS launch
         flow1.combine_with(flow2, 3)
         kernel_comb = _native.last_kernel_name()
-        return {"stream_s": stream_s, "cached_s": cached_s, "launches": k, "broadcast_ms": (bms[len(bms) // 2] if bms else None),
-                "rccl_ranks": ranks_seen, "kernel_apply": kernel_apply, "kernel_combine3": kernel_comb,
-                "apply_ms": sum(ta) / k, "comb_ms": sum(tc) / k, "apply_ms_median": ta[k // 2], "comb_ms_median": tc[k // 2],
-                "apply_ms_min": ta[0], "comb_ms_min": tc[0]}
+        res.update({"cached_s": cached_s, "launches": k, "kernel_apply": kernel_apply, "kernel_combine3": kernel_comb,
+                    "apply_ms": sum(ta) / k, "comb_ms": sum(tc) / k, "apply_ms_median": ta[k // 2], "comb_ms_median": tc[k // 2],
+                    "apply_ms_min": ta[0], "comb_ms_min": tc[0]})
+        return res
 
     def med(v):
         return sorted(v)[len(v) // 2]
 
-    blocks = args.blocks if args.blocks > 0 else max(5, -(-500 // args.steps))
-    r = measure(n, args.steps, args.warmup, rank, blocks)
-    t_apply, t_comb = r["apply_ms"], r["comb_ms"]
-    stream_blocks, cached_blocks = r["stream_s"], r["cached_s"]
+    blocks = args.blocks if args.blocks > 0 else (max(5, -(-500 // args.steps)) if args.full else 1)
+    r = measure(n, args.steps, args.warmup, rank, blocks, full=args.full)
+    outputs = r.pop("outputs")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+    del outputs
+    stream_blocks, cached_blocks = r["stream_s"], r.get("cached_s", [])
     if world > 1:                                  # every block's time is the MAX over the ranks
-        t = torch.tensor([stream_blocks, cached_blocks], dtype=torch.float64, device=dev)
+        t = torch.tensor(stream_blocks + cached_blocks, dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        stream_blocks, cached_blocks = [float(v) for v in t[0].tolist()], [float(v) for v in t[1].tolist()]
-    elapsed, el_cached = med(stream_blocks), med(cached_blocks)          # the median block is the reported one
+        t = [float(v) for v in t.tolist()]
+        stream_blocks, cached_blocks = t[:len(stream_blocks)], t[len(stream_blocks):]
+    elapsed = med(stream_blocks)                   # the median block is the reported one
+    el_cached = med(cached_blocks) if args.full else None
 
     weak = None
-    if world > 1 and args.scaling == "strong" and not args.no_weak and not args.shared_image:
+    if args.full and world > 1 and args.scaling == "strong" and not args.no_weak and not args.shared_image:
         # the weak-scaling figure beside the headline: B = --batch on EVERY GPU (a job `world` times as large)
         wk = measure(args.batch, args.steps, args.warmup, 100 + rank, max(3, blocks // 2))
         t = torch.tensor(wk["stream_s"], dtype=torch.float64, device=dev)
@@ -480,7 +555,7 @@ def main():
                 "value": round(args.batch * world * h * w / (wms * 1e-3) / 1e6, 1), "unit": "Mpix/s"}
 
     probe = None
-    if world == 1 and not args.no_probe and not args.shared_image and (n, h, w) == (64, 1080, 1920):
+    if args.full and world == 1 and not args.no_probe and not args.shared_image and (n, h, w) == (64, 1080, 1920):
         # BASELINE.json configs[3] on 8 GPUs leaves 8 elements per GPU: the same step at B = 8 on this GPU
         k8 = max(args.steps, 100)
         p8 = measure(8, k8, 5, 11, 5)
@@ -507,50 +582,18 @@ def main():
             probe["implied_speedup_at_8_gpus_" + key] = round((elapsed / args.steps * 1e3) / got["ms_per_step"], 2)
 
     secondary = None
-    if world == 1 and not args.no_secondary and rank == 0:
+    if args.full and world == 1 and not args.no_secondary and rank == 0:
         secondary = secondary_lines(ofl, dev)
 
-    # measured device-copy ceiling: a 1 GiB fp32 copy on the same stream, read + write bytes / time
-    a = torch.empty(1 << 28, dtype=torch.float32, device=dev)
-    b = torch.empty_like(a)
-    b.copy_(a)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(5):
-        b.copy_(a)
-    e1.record()
-    torch.cuda.synchronize()
-    copy_gbs = 5 * 2 * a.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    # a stream with the apply kernel's byte mix -- 22 bytes read for 13 written (flow 8 + image 12 + two masks | image 12 + mask 1) --
-    # as plain torch elementwise work: out[13 parts] = f(in[22 parts]) over 1 GiB; what a streaming kernel of this mix reaches here
-    parts = a.numel() // 22
-    src22, dst13 = a[:22 * parts].view(22, parts), b[:13 * parts].view(13, parts)
-    torch.add(src22[:13], src22[9:22], out=dst13)                       # (reads all 22 rows -- rows 9..12 twice, from cache -- writes 13)
-    e0.record()
-    for _ in range(5):
-        torch.add(src22[:13], src22[9:22], out=dst13)
-    e1.record()
-    torch.cuda.synchronize()
-    mix_gbs = 5 * 35 * parts * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    del a, b, src22, dst13
+    if args.full:
+        copy_gbs, mix_gbs = stream_probes(dev)
 
     if rank == 0:
-        traffic_source = "--traffic-bytes" if args.traffic_bytes is not None else None
-        if args.traffic_bytes is None and not args.shared_image and (n, h, w) == (64, 1080, 1920):
-            for name in ("r6_traffic.json", "r5_traffic.json", "r4_traffic.json", "r3_traffic.json", "r2_traffic.json", "r1_traffic.json"):   # PMC passes are separate runs (tools/refresh_profiles_r5.sh)
-                tj = os.path.join(ROOT, "profiles", name)
-                if os.path.exists(tj):
-                    with open(tj) as fh:
-                        args.traffic_bytes = json.load(fh).get("traffic_bytes_per_launch")
-                    traffic_source = ("profiles/%s: an EARLIER rocprofv3 --pmc pass of this command (2 x FETCH_SIZE + WRITE_SIZE per "
-                                      "launch, MI355X_MICROARCH.md gfx950 correction), not measured in this run" % name)
-                    break
         px = n * h * w
         gpx = global_batch * h * w
         ms_step = elapsed / args.steps * 1e3
         # --shared-image: the B = 1 image + target mask (13 B/px) are read once per launch, not once per batch element
         bytes_apply = (BYTES_APPLY - 13) + 13.0 / max(n, 1) if args.shared_image else BYTES_APPLY
-        ach = bytes_apply * px / (t_apply * 1e-3) / 1e9
         per_step = sorted(b / args.steps * 1e3 for b in stream_blocks)
         out = {
             "metric": "Mpix/s warped+composed (Flow(...) x2 from raw tensors, Flow.apply 't' C=3 + valid area, then "
@@ -573,27 +616,40 @@ def main():
                        "ms_per_step_min": round(per_step[0], 4), "ms_per_step_median": round(per_step[len(per_step) // 2], 4),
                        "ms_per_step_max": round(per_step[-1], 4),
                        "value_min": round(gpx / (per_step[-1] * 1e-3) / 1e6, 1), "value_max": round(gpx / (per_step[0] * 1e-3) / 1e6, 1)},
-            "roofline": {"bound": "hbm", "kernel": r["kernel_apply"] + " (Flow.apply 't'; the name the library reports for the launch: ofl_last_kernel_name)",
-                         "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(ach / HBM_PEAK_GBS, 4),
-                         "traffic": args.traffic_bytes,
-                         "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_launch": int(bytes_apply * px),
-                         "avg_launch_ms": round(t_apply, 4), "median_launch_ms": round(r["apply_ms_median"], 4),
-                         "min_launch_ms": round(r["apply_ms_min"], 4), "launches_timed": r["launches"],
-                         "device_copy_GBs": round(copy_gbs, 1),
-                         "read_mostly_stream_GBs": round(mix_gbs, 1),
-                         "read_mostly_stream_note": "torch.add over 1 GiB with the apply kernel's byte mix (22 B read : 13 B written); a same-box "
-                                                    "reference point for a streaming kernel of that mix, not a ceiling"},
             "rccl_ranks": r["rccl_ranks"],
-            "kernels": {"apply_kernel": r["kernel_apply"], "combine3_kernel": r["kernel_combine3"],
-                        "apply_ms": round(t_apply, 4), "apply_GBs": round(ach, 1),
-                        "combine3_ms": round(t_comb, 4), "combine3_ms_median": round(r["comb_ms_median"], 4),
-                        "combine3_GBs": round(BYTES_COMBINE * px / (t_comb * 1e-3) / 1e9, 1),
-                        "combine3_frac": round(BYTES_COMBINE * px / (t_comb * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                        "validation_ms_per_step": round(ms_step - el_cached / args.steps * 1e3, 4)},
-            "value_cached_flow_objects": round(gpx / (el_cached / args.steps) / 1e6, 1),
         }
+        if args.full:
+            t_apply, t_comb = r["apply_ms"], r["comb_ms"]
+            ach = bytes_apply * px / (t_apply * 1e-3) / 1e9
+            traffic_source = "--traffic-bytes" if args.traffic_bytes is not None else None
+            if args.traffic_bytes is None and not args.shared_image and (n, h, w) == (64, 1080, 1920):
+                for name in ("r6_traffic.json", "r5_traffic.json", "r4_traffic.json", "r3_traffic.json", "r2_traffic.json", "r1_traffic.json"):   # PMC passes are separate runs (tools/refresh_profiles_r5.sh)
+                    tj = os.path.join(ROOT, "profiles", name)
+                    if os.path.exists(tj):
+                        with open(tj) as fh:
+                            args.traffic_bytes = json.load(fh).get("traffic_bytes_per_launch")
+                        traffic_source = ("profiles/%s: an EARLIER rocprofv3 --pmc pass of this command (2 x FETCH_SIZE + WRITE_SIZE per "
+                                          "launch, MI355X_MICROARCH.md gfx950 correction), not measured in this run" % name)
+                        break
+            out["roofline"] = {"bound": "hbm", "kernel": r["kernel_apply"] + " (Flow.apply 't'; the name the library reports for the launch: ofl_last_kernel_name)",
+                               "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(ach / HBM_PEAK_GBS, 4),
+                               "traffic": args.traffic_bytes,
+                               "traffic_source": traffic_source,
+                               "algorithmic_bytes_per_launch": int(bytes_apply * px),
+                               "avg_launch_ms": round(t_apply, 4), "median_launch_ms": round(r["apply_ms_median"], 4),
+                               "min_launch_ms": round(r["apply_ms_min"], 4), "launches_timed": r["launches"],
+                               "device_copy_GBs": round(copy_gbs, 1),
+                               "read_mostly_stream_GBs": round(mix_gbs, 1),
+                               "read_mostly_stream_note": "torch.add over 1 GiB with the apply kernel's byte mix (22 B read : 13 B written); a same-box "
+                                                          "reference point for a streaming kernel of that mix, not a ceiling"}
+            out["kernels"] = {"apply_kernel": r["kernel_apply"], "combine3_kernel": r["kernel_combine3"],
+                              "apply_ms": round(t_apply, 4), "apply_GBs": round(ach, 1),
+                              "combine3_ms": round(t_comb, 4), "combine3_ms_median": round(r["comb_ms_median"], 4),
+                              "combine3_GBs": round(BYTES_COMBINE * px / (t_comb * 1e-3) / 1e9, 1),
+                              "combine3_frac": round(BYTES_COMBINE * px / (t_comb * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                              "validation_ms_per_step": round(ms_step - el_cached / args.steps * 1e3, 4)}
+            out["value_cached_flow_objects"] = round(gpx / (el_cached / args.steps) / 1e6, 1)
         if args.n1_ms is not None:
             out["speedup_vs_n1"] = round(args.n1_ms / ms_step, 3)
         if weak is not None:
@@ -606,7 +662,7 @@ def main():
             out["secondary"] = secondary
         if probe is not None:
             out["strong_scaling_probe"] = probe
-        if not args.no_cpu_baseline and world == 1:          # (the CPU baseline is a single-node, N = 1 figure)
+        if args.full and not args.no_cpu_baseline and world == 1:          # (the CPU baseline is a single-node, N = 1 figure)
             # 64 OpenMP threads is where the oracle peaks on the 2 x 64-core host of the GPU box (tools/cpu_threads_probe.py)
             out["cpu_baseline"] = cpu_baseline(h, w, args.cpu_seconds, min(os.cpu_count() or 1, 64))
         print(json.dumps(out))

@@ -305,7 +305,7 @@ def test_bench_starts_its_own_ranks_when_not_under_a_launcher(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--self-launch", "--steps", "3", "--warmup", "1", "--batch", "4",
-           "--no-cpu-baseline", "--no-probe", "--no-secondary", "--blocks", "1", "--n1-ms", "1.0"]
+           "--full", "--no-cpu-baseline", "--no-probe", "--no-secondary", "--blocks", "1", "--n1-ms", "1.0"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     import json
@@ -336,6 +336,35 @@ def test_bench_shared_image_and_ragged_strong_scaling_under_torch_distributed_ru
     assert out["n_gpus"] == 1 and out["value"] > 0 and out["scaling"] == "strong" and out["config"]["global_batch"] == 5
     assert "broadcast" in out["config"]["parallelism"] and out["broadcast_ms"] is not None and out["broadcast_ms"] > 0
     assert abs(out["config"]["bytes_per_px"] - (22 + 13 / 5 + 27)) < 1e-2
+
+
+def test_plain_bench_times_exactly_its_steps_and_dumps_what_the_last_one_returned(dev, tmp_path):
+    """A plain `bench.py` run times ONE block of exactly --steps steps and prints the headline only; `--dump-outputs DIR` writes
+    what the last timed step returned.  Those arrays equal the oracle's on the same seeded inputs, put through the same
+    sampler (warped and combined_vecs are larger than bench.DUMP_ELEMS here, the masks are not)."""
+    import json
+    import bench
+    from oracle import oracle
+    n, h, w = 2, 600, 1000
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--batch", str(n),
+           "--height", str(h), "--width", str(w), "--dump-outputs", str(tmp_path / "gpu")]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    out = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 4 and out["timing"]["blocks"] == 1 and out["timing"]["steps_per_block"] == 4 and out["ms_per_step"] > 0
+    assert not {"roofline", "kernels", "value_cached_flow_objects", "secondary", "strong_scaling_probe", "cpu_baseline"} & set(out)
+    f1, f2, img, m1, m2, tm = [t.cpu().numpy() for t in bench.make_inputs(n, h, w, dev, 0)]
+    ow, ov = oracle.flow_apply(f2, 't', m2, img, tm)
+    oc, ocm, _ = oracle.combine_with(f1, m1, f2, m2, 3, 't')
+    exp = {"warped": ow, "valid": ov, "combined_vecs": oc, "combined_mask": ocm}
+    bench.dump_outputs(str(tmp_path / "oracle"), {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in exp.items()})
+    total = 0
+    for name, full in exp.items():
+        got, want = np.load(tmp_path / "gpu" / (name + ".npy")), np.load(tmp_path / "oracle" / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == (full.shape if full.size <= bench.DUMP_ELEMS else (bench.DUMP_ELEMS,)), name
+        assert np.array_equal(got, want), name
+        total += os.path.getsize(tmp_path / "gpu" / (name + ".npy"))
+    assert total <= 64 << 20
 
 
 def test_kernel_outputs_keep_their_flag_words_under_inference_mode(dev, monkeypatch):

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 root=$PWD
 out="$root/gpurun_out/prof_$tag"
 mkdir -p "$out"
-CMD=(python3 "$root/bench.py" --steps 10 --warmup 2 --no-cpu-baseline)
+CMD=(python3 "$root/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline)
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -- "${CMD[@]}" > "$out/stats.log" 2>&1)
 for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "l2 TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum"; do
   set -- $pass; name=$1; shift

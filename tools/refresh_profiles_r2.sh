@@ -5,14 +5,14 @@ export TMPDIR=/tmp
 R=$PWD
 O=$R/gpurun_out/r2final
 mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 # rocprofv3 kernel statistics of the bench command
-(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-probe > $O/bench_stats.log 2>&1)
+(cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-probe > $O/bench_stats.log 2>&1)
 f=$(ls $O/bench_stats/*/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp $f $O/bench_kernel_stats.csv
 # PMC traffic passes of the bench command (separate passes, --kernel-trace only)
 for pass in "fetch FETCH_SIZE" "write WRITE_SIZE"; do
   set -- $pass; name=$1; shift
-  (cd /tmp && timeout 600 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/bench_$name -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-probe > $O/bench_$name.log 2>&1)
+  (cd /tmp && timeout 600 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/bench_$name -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-probe > $O/bench_$name.log 2>&1)
 done
 python3 tools/pmc_summary.py $O warp_bwd > $O/bench_pmc_summary.txt 2>&1
 # the other operations

@@ -6,8 +6,8 @@ export TMPDIR=/tmp
 R=$PWD
 O=$R/gpurun_out/r4final
 mkdir -p $O
-python bench.py > $O/bench.json 2> $O/bench.err
-BENCH="python3 $R/bench.py --steps 20 --warmup 3 --blocks 1 --no-cpu-baseline --no-probe --no-secondary"
+python bench.py --full > $O/bench.json 2> $O/bench.err
+BENCH="python3 $R/bench.py --full --steps 20 --warmup 3 --blocks 1 --no-cpu-baseline --no-probe --no-secondary"
 (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- $BENCH > $O/bench_stats.log 2>&1)
 f=$(ls $O/bench_stats/*/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp $f $O/bench_kernel_stats.csv
 for pass in "fetch FETCH_SIZE" "write WRITE_SIZE"; do
