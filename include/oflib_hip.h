@@ -512,6 +512,36 @@ int ofl_flow_from_matrix_f32(const float* matrices, int64_t matrix_bs, float sig
  */
 int ofl_flag_words_or_i32(const int32_t* words, int32_t n, int32_t* out, void* stream);
 
+/*
+ * Flow.visualise (flow_class.py:1246-1356) and visualise_flow (flow_operations.py:339-367): the HSV colour coding of a flow.
+ * ofl_visualise.hip; bit-exact with the reference's NumPy / OpenCV host code (cv2.cartToPolar restated from OpenCV 4.x, its FMA form).
+ *
+ * ofl_visualise_workspace_ints(n): int32 words of the workspace ofl_visualise_range_f32 needs for n images (OFL_E_SHAPE if n is
+ *   out of [1, 65535]).  The workspace is cleared inside the call (one hipMemsetAsync on `stream`).
+ *
+ * ofl_visualise_range_f32 <- the `range_max is None` branch (flow_class.py:1300-1309): per image, np.percentile(m, 99) (numpy 2.2.6,
+ *   'linear', computed in fp32 as numpy computes it for fp32 input), else np.max(m) if that is > 0, else 1, over the magnitudes m of
+ *   the thresholded flow (utils.py:623-643, strict fp32 test against 1e-3) -- all pixels, or the pixels where mask != 0 when `mask`
+ *   is given (show_mask).  An exact order statistic (radix select on the fp32 bit patterns, integer histograms): bitwise
+ *   reproducible.  flow [N,2,H,W] fp32 (flow_half = 0) or fp16 (flow_half = 1) with batch stride flow_bs (elements), mask
+ *   [N,H,W] bytes or NULL, workspace int32[ofl_visualise_workspace_ints(n)], range_max float64[N] out, counts int32[N] out (the
+ *   number of values per image; optional).  An image with no counted pixel gets range_max 1 and count 0: the caller raises numpy's
+ *   IndexError for it.
+ *
+ * ofl_visualise_u8 <- flow_class.py:1287-1349: threshold, cartToPolar, hue = mod(angle, 360) / 2, value 255 (180 where show_mask
+ *   and the mask is False), saturation clip(float64(mag * 255) / range_max, 0, 255) stored as fp32, mask borders
+ *   (show_mask_borders: findContours + drawContours of :1323-1327 = the True pixels with a False 4-neighbour or on the image edge)
+ *   set to 0, then mode 0 = 'hsv' (np.round of the planes), 1 = 'rgb', 2 = 'bgr' (the float64 HSV -> RGB of :1333-1349, rounded half
+ *   to even).  mask NULL = all True.  range_max float64[N] DEVICE memory (ofl_visualise_range_f32's output, or the caller's values).
+ *   out uint8: layout 0 = [N,3,H,W] planes (the tensor the reference returns), 1 = [N,H,W,3] (its NumPy array), contiguous.
+ */
+int64_t ofl_visualise_workspace_ints(int32_t n);
+int ofl_visualise_range_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
+                            int32_t* workspace, double* range_max, int32_t* counts, int32_t n, int32_t h, int32_t w, void* stream);
+int ofl_visualise_u8(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, int32_t show_mask,
+                     int32_t show_mask_borders, const double* range_max, int32_t mode, int32_t layout, uint8_t* out, int32_t n,
+                     int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

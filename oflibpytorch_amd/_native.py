@@ -18,7 +18,7 @@ import torch
 from . import _build
 
 FLAG_NONFINITE, FLAG_NZ, FLAG_NZ_THR, FLAG_NZ_MASKED, FLAG_NZ_THR_MASKED = 1, 2, 4, 8, 16
-ABI_VERSION = 33              # ofl_version() of the library this file's argtypes describe
+ABI_VERSION = 34              # ofl_version() of the library this file's argtypes describe
 ROUND_NONE, ROUND_RINT, ROUND_U8 = 0, 1, 2
 THRESHOLD = 1e-3
 
@@ -26,7 +26,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_splat_tiled_f32", "ofl_flow_flags_f32", "ofl_warp_bwd_u8", "ofl_flow_from_f16",
             "ofl_warp_bwd_grad_f32", "ofl_splat_grad_f32", "ofl_sample_pts_f32", "ofl_sample_pts_grad_f32",
             "ofl_flow_extents_f32", "ofl_flag_words_or_i32", "ofl_splat_sum_f32", "ofl_warp_bwd_win_f32", "ofl_splat_tiled_win_f32", "ofl_splat_tiled_f16",
-            "ofl_warp_bwd_h_f32", "ofl_flow_flags_host", "ofl_host_words_alloc", "ofl_host_words_free", "ofl_flow_from_matrix_f32", "ofl_splat_tiled_fallback_images", "ofl_warp_valid_f32", "ofl_resize_bilinear_f32", "ofl_splat_tile_geometry", "ofl_splat_gather_info", "ofl_last_kernel_name")
+            "ofl_warp_bwd_h_f32", "ofl_flow_flags_host", "ofl_host_words_alloc", "ofl_host_words_free", "ofl_flow_from_matrix_f32", "ofl_splat_tiled_fallback_images", "ofl_warp_valid_f32", "ofl_resize_bilinear_f32", "ofl_splat_tile_geometry", "ofl_splat_gather_info", "ofl_last_kernel_name",
+            "ofl_visualise_workspace_ints", "ofl_visualise_range_f32", "ofl_visualise_u8")
 _lib = None
 
 
@@ -99,9 +100,13 @@ def load_library(path: str = None):
     lib.ofl_host_words_alloc.argtypes = [i64, ctypes.POINTER(ctypes.c_void_p)]
     lib.ofl_host_words_free.argtypes = [p]
     lib.ofl_flow_from_matrix_f32.argtypes = [p, i64, f32, p, i32, i32, i32, p]
+    lib.ofl_visualise_workspace_ints.argtypes = [i32]
+    lib.ofl_visualise_range_f32.argtypes = [p, i64, i32, p, i64, p, p, p, i32, i32, i32, p]
+    lib.ofl_visualise_u8.argtypes = [p, i64, i32, p, i64, i32, i32, p, i32, i32, p, i32, i32, i32, p]
     for name in _SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     lib.ofl_splat_tiled_workspace_ints.restype = ctypes.c_int64
+    lib.ofl_visualise_workspace_ints.restype = ctypes.c_int64
     lib.ofl_last_kernel_name.restype = ctypes.c_char_p
     lib.ofl_last_kernel_name.argtypes = []
     lib.ofl_splat_tiled_pass_images.restype = ctypes.c_int64
@@ -950,6 +955,57 @@ def warp_valid(flow, mask, flow_sign: float = 1.0, thr: float = 0.9999) -> torch
         out = torch.empty((n, h, w), dtype=torch.bool, device=dev)
         _check(lib.ofl_warp_valid_f32(_ptr(f), fbs, float(flow_sign), _ptr(m), mbs, float(thr), _ptr(out), n, h, w, _stream(dev)),
                "ofl_warp_valid_f32")
+    return out
+
+
+# -- Flow.visualise (flow_class.py:1246-1356): ofl_visualise.hip ----------------------------------------------------------------
+VIS_MODES = {'hsv': 0, 'rgb': 1, 'bgr': 2}
+VIS_PLANES, VIS_INTERLEAVED = 0, 1
+
+
+def _vis_flow(vecs: torch.Tensor, dev, n: int):
+    """The flow as the visualise kernels read it: fp16 planes of an fp16-stored flow as they are, anything else as fp32."""
+    if vecs.dtype == torch.float16:
+        v, vbs = _planes(vecs.detach(), dev, torch.float16, n, "flow")
+        return v, vbs, 1
+    v, vbs = _planes(vecs.detach(), dev, torch.float32, n, "flow")
+    return v, vbs, 0
+
+
+def visualise_range(vecs: torch.Tensor, mask: torch.Tensor = None):
+    """The default `range_max` of Flow.visualise (flow_class.py:1300-1309) on the device: per image the 99th percentile of the
+    thresholded magnitudes (all pixels, or those under `mask`), else their max, else 1 (ofl_visualise_range_f32).  Returns
+    (float64[N], int32[N] counts of the values per image), both on the HIP device; nothing is read back."""
+    lib, dev = load_library(), device(vecs, mask)
+    n, _, h, w = vecs.shape
+    with _on(dev):
+        v, vbs, half = _vis_flow(vecs, dev, n)
+        m, mbs = (None, 0) if mask is None else _planes(mask, dev, torch.bool, n, "mask")
+        ws = torch.empty(int(lib.ofl_visualise_workspace_ints(n)), dtype=torch.int32, device=dev)
+        rng = torch.empty(n, dtype=torch.float64, device=dev)
+        counts = torch.empty(n, dtype=torch.int32, device=dev)
+        _check(lib.ofl_visualise_range_f32(_ptr(v), vbs, half, _ptr(m), mbs, _ptr(ws), _ptr(rng), _ptr(counts), n, h, w,
+                                           _stream(dev)), "ofl_visualise_range_f32")
+    return rng, counts
+
+
+def visualise(vecs: torch.Tensor, range_max, mode: str, mask: torch.Tensor = None, show_mask: bool = False,
+              show_mask_borders: bool = False, layout: int = VIS_PLANES) -> torch.Tensor:
+    """The colour image of Flow.visualise (ofl_visualise_u8): uint8 [N,3,H,W] (layout VIS_PLANES) or [N,H,W,3]
+    (VIS_INTERLEAVED) on the HIP device.  `range_max`: float64 values per image (a device tensor, e.g. visualise_range's, or
+    anything torch.as_tensor takes); `mask` None = all True."""
+    lib, dev = load_library(), device(vecs, mask)
+    n, _, h, w = vecs.shape
+    with _on(dev):
+        v, vbs, half = _vis_flow(vecs, dev, n)
+        m, mbs = (None, 0) if mask is None else _planes(mask, dev, torch.bool, n, "mask")
+        rng = torch.as_tensor(range_max, dtype=torch.float64).to(dev).contiguous()
+        if rng.numel() != n:
+            raise ValueError("oflibpytorch_amd: %d range_max values for %d images" % (rng.numel(), n))
+        shape = (n, 3, h, w) if layout == VIS_PLANES else (n, h, w, 3)
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        _check(lib.ofl_visualise_u8(_ptr(v), vbs, half, _ptr(m), mbs, int(bool(show_mask)), int(bool(show_mask_borders)),
+                                    _ptr(rng), VIS_MODES[mode], int(layout), _ptr(out), n, h, w, _stream(dev)), "ofl_visualise_u8")
     return out
 
 

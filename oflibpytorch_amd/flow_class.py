@@ -955,6 +955,55 @@ class Flow(object):
         return torch.tensor([(f & bit) == 0 for f in self._flags()], dtype=torch.bool, device=self._device)
 
     # ------------------------------------------------------------------------------------------
+    # visualisation (flow_class.py:1246-1356)
+    # ------------------------------------------------------------------------------------------
+    def visualise(self, mode: str, show_mask: bool = None, show_mask_borders: bool = None,
+                  range_max: Union[float, int, list, tuple] = None, return_tensor: bool = None):
+        """The flow as an 'rgb' / 'bgr' / 'hsv' image (hue: direction, saturation: magnitude / range_max, value 180 outside
+        the mask if `show_mask`, mask borders black if `show_mask_borders`).  `range_max` defaults to the 99th percentile of
+        the magnitudes per batch element (under the mask if `show_mask`).  Returns a uint8 tensor N-3-H-W on the flow's
+        device, or a NumPy array N-H-W-3 if `return_tensor` is False; 'hsv' is always a NumPy array N-H-W-3, as in the
+        reference.  Computed by two HIP kernels (ofl_visualise.hip), bit-exact with the reference's NumPy / OpenCV host code;
+        not differentiable, as in the reference."""
+        show_mask = False if show_mask is None else show_mask
+        show_mask_borders = False if show_mask_borders is None else show_mask_borders
+        return_tensor = True if return_tensor is None else return_tensor
+        if not isinstance(show_mask, bool):
+            raise TypeError("Error visualising flow: Show_mask needs to be boolean")
+        if not isinstance(show_mask_borders, bool):
+            raise TypeError("Error visualising flow: Show_mask_borders needs to be boolean")
+        if not isinstance(return_tensor, bool):
+            raise TypeError("Error visualising flow: Return_tensor needs to be boolean")
+        self._require_finite("Error visualising flow: ")
+        vecs, mask = self._fv, self._mask            # (no mask: all True, never materialised)
+        n = self.shape[0]
+        if range_max is None:
+            rng, counts = _native.visualise_range(vecs, mask if show_mask else None)
+            if show_mask and mask is not None and int(counts.min()) == 0:
+                # np.percentile of an empty selection (flow_class.py:1304)
+                raise IndexError("index -1 is out of bounds for axis 0 with size 0")
+        else:
+            # flow_class.py:1310-1320, the same NumPy expressions on the N values
+            if isinstance(range_max, (list, tuple)):
+                if len(range_max) != n:
+                    raise TypeError("Error visualising flow: Range_max list or tuple length ({}) needs to match the flow "
+                                    "batch size ({})".format(len(range_max), n))
+                range_max = np.array(range_max)
+            elif isinstance(range_max, (float, int)):
+                range_max = np.array([range_max for _ in range(n)])
+            else:
+                raise TypeError("Error visualising flow: Range_max needs to be an integer, a float, a list, or a tuple")
+            if any(range_max <= 0):
+                raise ValueError("Error visualising flow: Range_max needs to be larger than zero")
+            rng = np.asarray(range_max, dtype=np.float64)
+        if not isinstance(mode, str) or mode not in _native.VIS_MODES:
+            raise ValueError("Error visualising flow: Mode needs to be either 'bgr', 'rgb', or 'hsv'")
+        kw = dict(mask=mask, show_mask=show_mask and mask is not None, show_mask_borders=show_mask_borders)
+        if mode == 'hsv' or not return_tensor:
+            return _native.visualise(vecs, rng, mode, layout=_native.VIS_INTERLEAVED, **kw).cpu().numpy()
+        return _native.visualise(vecs, rng, mode, layout=_native.VIS_PLANES, **kw).to(self._device)
+
+    # ------------------------------------------------------------------------------------------
     # composition (flow_class.py:1648-1810)
     # ------------------------------------------------------------------------------------------
     def combine_with(self, flow: FlowAlias, mode: int, thresholded: bool = None) -> FlowAlias:
@@ -1177,6 +1226,6 @@ def _combine_plan(mode: int, self_ref: str, other_ref: str, out_ref: str) -> _Co
 
 # the public methods that read a flow's flag word: each starts a new validation epoch under set_revalidate_every_call(True)
 for _name in ('apply', 'track', 'switch_ref', 'invert', 'valid_target', 'valid_source', 'get_padding', 'is_zero', 'combine_with',
-              'combine'):
+              'combine', 'visualise'):
     setattr(Flow, _name, _public(getattr(Flow, _name)))
 del _name

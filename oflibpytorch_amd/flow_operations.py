@@ -1,5 +1,5 @@
 """Tensor-level wrappers round the `Flow` methods of the hot path (reference
-``src/oflibpytorch/flow_operations.py:84-277, 458-483``): same signatures, 3-D in -> 3-D out."""
+``src/oflibpytorch/flow_operations.py:84-277, 339-367, 458-483``): same signatures, 3-D in -> 3-D out."""
 from typing import Union
 
 import numpy as np
@@ -56,6 +56,12 @@ def get_flow_padding(flow, ref: str) -> list:
     (flow_operations.py:280-303)"""
     p = Flow(flow, ref).get_padding()
     return p if len(flow.shape) > 3 else p[0]
+
+
+def visualise_flow(flow, mode: str, range_max: float = None, return_tensor: bool = None):
+    """Flow(flow).visualise(mode, range_max=..., return_tensor=...), 3-D in -> 3-D out (flow_operations.py:339-367)"""
+    v = Flow(flow).visualise(mode=mode, range_max=range_max, return_tensor=return_tensor)
+    return v if len(flow.shape) > 3 else v.squeeze(0)
 
 
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
