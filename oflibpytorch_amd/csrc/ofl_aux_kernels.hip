@@ -19,6 +19,10 @@
 
 #pragma clang fp contract(off)
 
+// the launch recorder of ofl_kernels.hip (ofl_last_kernel_name): the launchers below report the kernel they ran too
+extern const void* g_ofl_last_kernel;
+#define OFL_KLAUNCH(K, ...) do { g_ofl_last_kernel = (const void*)(K); hipLaunchKernelGGL(K, __VA_ARGS__); } while (0)
+
 namespace {
 
 constexpr float kZeroThr = 1e-3f;   // utils.py:23, :642
@@ -523,7 +527,7 @@ __attribute__((visibility("default"))) int ofl_warp_bwd_grad_f32(
     p.gout = grad_out; p.g_scale = g_scale; p.gsrc = grad_src; p.gsrc_bs = grad_src_bs; p.gflow = grad_flow;
     p.n = n; p.c = c; p.h = h; p.w = w;
     p.wm1 = (float)(w - 1); p.hm1 = (float)(h - 1); p.half_wm1 = p.wm1 / 2.0f; p.half_hm1 = p.hm1 / 2.0f;
-    hipLaunchKernelGGL(warp_grad_kernel, dim3(blocks_for((int64_t)h * w, n), (unsigned)n), dim3(256), 0, (hipStream_t)stream, p);
+    OFL_KLAUNCH(warp_grad_kernel, dim3(blocks_for((int64_t)h * w, n), (unsigned)n), dim3(256), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 
@@ -546,8 +550,8 @@ __attribute__((visibility("default"))) int ofl_splat_grad_f32(
     p.out = out; p.density = density; p.gout = grad_out; p.gden = grad_density; p.gdata = grad_data; p.gxy = grad_xy;
     p.prep = scratch;
     p.n = n; p.c = c; p.h = h; p.w = w;
-    hipLaunchKernelGGL(splat_grad_prep_kernel, dim3(blocks_for((int64_t)h * w, n), (unsigned)n), dim3(256), 0, (hipStream_t)stream, p);
-    hipLaunchKernelGGL(splat_grad_kernel, dim3(blocks_for((int64_t)h * w, n), (unsigned)n), dim3(256), 0, (hipStream_t)stream, p);
+    OFL_KLAUNCH(splat_grad_prep_kernel, dim3(blocks_for((int64_t)h * w, n), (unsigned)n), dim3(256), 0, (hipStream_t)stream, p);
+    OFL_KLAUNCH(splat_grad_kernel, dim3(blocks_for((int64_t)h * w, n), (unsigned)n), dim3(256), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 
@@ -571,7 +575,7 @@ __attribute__((visibility("default"))) int ofl_sample_pts_f32(const float* flow,
     if (rc) return rc;
     if (!out) return OFL_E_NULL;
     p.out = out;
-    hipLaunchKernelGGL(sample_pts_kernel<false>, dim3(blocks_for(m, n), (unsigned)n), dim3(256), 0, (hipStream_t)stream, p);
+    OFL_KLAUNCH((sample_pts_kernel<false>), dim3(blocks_for(m, n), (unsigned)n), dim3(256), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 
@@ -585,7 +589,7 @@ __attribute__((visibility("default"))) int ofl_sample_pts_grad_f32(const float* 
     if (!grad_out) return OFL_E_NULL;
     if (!grad_flow && !grad_pts) return OFL_E_ARG;
     p.gout = grad_out; p.gflow = grad_flow; p.gpts = grad_pts;
-    hipLaunchKernelGGL(sample_pts_kernel<true>, dim3(blocks_for(m, n), (unsigned)n), dim3(256), 0, (hipStream_t)stream, p);
+    OFL_KLAUNCH((sample_pts_kernel<true>), dim3(blocks_for(m, n), (unsigned)n), dim3(256), 0, (hipStream_t)stream, p);
     return (int)hipGetLastError();
 }
 
@@ -596,7 +600,7 @@ __attribute__((visibility("default"))) int ofl_resize_bilinear_f32(const float* 
     if (planes < 1 || h < 1 || w < 1 || oh < 1 || ow < 1 || planes > 65535) return OFL_E_SHAPE;
     if ((int64_t)h * w >= (1ll << 31) || (int64_t)oh * ow >= (1ll << 31)) return OFL_E_SHAPE;
     if (!(rcp_scale_h > 0.0f) || !(rcp_scale_w > 0.0f)) return OFL_E_ARG;
-    hipLaunchKernelGGL(resize_bilinear_kernel, dim3(blocks_for((int64_t)oh * ow, planes), (unsigned)planes), dim3(256), 0,
+    OFL_KLAUNCH(resize_bilinear_kernel, dim3(blocks_for((int64_t)oh * ow, planes), (unsigned)planes), dim3(256), 0,
                        (hipStream_t)stream, src, dst, h, w, oh, ow, rcp_scale_h, rcp_scale_w);
     return (int)hipGetLastError();
 }
@@ -615,8 +619,8 @@ __attribute__((visibility("default"))) int ofl_warp_valid_f32(const float* flow,
     const int64_t hw = (int64_t)h * w;
     const bool vec = (w & 3) == 0 && (flow_bs & 3) == 0 && (reinterpret_cast<uintptr_t>(flow) & 3) == 0;
     hipStream_t st = (hipStream_t)stream;
-    if (vec) hipLaunchKernelGGL(warp_valid_kernel<true>, dim3(blocks_for(hw / 4, n), (unsigned)n), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(warp_valid_kernel<false>, dim3(blocks_for(hw, n), (unsigned)n), dim3(256), 0, st, p);
+    if (vec) OFL_KLAUNCH((warp_valid_kernel<true>), dim3(blocks_for(hw / 4, n), (unsigned)n), dim3(256), 0, st, p);
+    else OFL_KLAUNCH((warp_valid_kernel<false>), dim3(blocks_for(hw, n), (unsigned)n), dim3(256), 0, st, p);
     return (int)hipGetLastError();
 }
 
@@ -629,8 +633,9 @@ __attribute__((visibility("default"))) int ofl_flow_extents_f32(const float* flo
     if (rc) return rc;
     if (!(sign == 1.0f || sign == -1.0f)) return OFL_E_ARG;
     hipStream_t st = (hipStream_t)stream;
+    // (the init / decode helpers launch unrecorded: the reduction names the call)
     hipLaunchKernelGGL(flow_extents_init_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, workspace, n);
-    hipLaunchKernelGGL(flow_extents_kernel, dim3(blocks_for((int64_t)h * w, n), (unsigned)n), dim3(256), 0, st, flow, flow_bs,
+    OFL_KLAUNCH(flow_extents_kernel, dim3(blocks_for((int64_t)h * w, n), (unsigned)n), dim3(256), 0, st, flow, flow_bs,
                        mask, mask_bs, sign, workspace, h, w);
     hipLaunchKernelGGL(flow_extents_decode_kernel, dim3((unsigned)((5 * n + 63) / 64)), dim3(64), 0, st, workspace, extents, n);
     return (int)hipGetLastError();
@@ -686,7 +691,7 @@ __global__ void flag_words_or_kernel(const int32_t* __restrict__ words, int32_t 
 __attribute__((visibility("default"))) int ofl_flag_words_or_i32(const int32_t* words, int32_t n, int32_t* out, void* stream) {
     if (!words || !out) return OFL_E_NULL;
     if (n < 1) return OFL_E_SHAPE;
-    hipLaunchKernelGGL(flag_words_or_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, words, n, out);
+    OFL_KLAUNCH(flag_words_or_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, words, n, out);
     return (int)hipGetLastError();
 }
 
@@ -697,7 +702,7 @@ __attribute__((visibility("default"))) int ofl_flow_from_matrix_f32(const float*
     if (!(sign == 1.0f || sign == -1.0f)) return OFL_E_ARG;
     int64_t bx = ((int64_t)h * ((w + 3) / 4) + 255) / 256;
     if (bx > 2048) bx = 2048;
-    hipLaunchKernelGGL(flow_from_matrix_kernel, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, (hipStream_t)stream, matrices, matrix_bs, sign,
+    OFL_KLAUNCH(flow_from_matrix_kernel, dim3((unsigned)bx, (unsigned)n), dim3(256), 0, (hipStream_t)stream, matrices, matrix_bs, sign,
                        dst, h, w);
     return (int)hipGetLastError();
 }

@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 import case_runner
+from grad_ref import _ref_apply_t, _ref_splat
 
 
 def _smooth(n, h, w, sigma, seed):
@@ -72,35 +73,6 @@ def dev():
     from oflibpytorch_amd import _native
     _native.load_library()
     return torch.device('cuda', 0)
-
-
-def _ref_apply_t(flow, target):
-    """utils.py:541-555 restated with torch ops on the device (autograd through grid_sample)."""
-    n, _, h, w = flow.shape
-    gy, gx = torch.meshgrid(torch.arange(h, device=flow.device), torch.arange(w, device=flow.device), indexing='ij')
-    grid = torch.stack((gx, gy), dim=-1).float().unsqueeze(0)
-    field = (grid - flow.permute(0, 2, 3, 1)) * 2
-    field = torch.stack((field[..., 0] / (w - 1), field[..., 1] / (h - 1)), dim=-1) - 1
-    return F.grid_sample(target.expand(n, -1, -1, -1), field, align_corners=True)
-
-
-def _ref_splat(x, y, data, mask):
-    """utils.py:1098-1144 restated with torch ops on the device (autograd through the weights and scatter_add_)."""
-    n, c, h, w = data.shape
-    x0, y0 = torch.floor(x), torch.floor(y)
-    xx, yy = torch.stack((x0, x0 + 1), -1), torch.stack((y0, y0 + 1), -1)
-    xs, ys = torch.clamp(xx, 0, w - 1), torch.clamp(yy, 0, h - 1)
-    wx = torch.stack((xx[..., 1] - x, x - xx[..., 0]), -1) * torch.eq(xx, xs).float()
-    wy = torch.stack((yy[..., 1] - y, y - yy[..., 0]), -1) * torch.eq(yy, ys).float()
-    wgt = torch.matmul(wy.unsqueeze(-1), wx.unsqueeze(-2)).permute(0, 3, 4, 1, 2).reshape(n * 4, h * w)
-    pos = ((w * ys).unsqueeze(-1) + xs.unsqueeze(-2)).permute(0, 3, 4, 1, 2).reshape(n * 4, h * w)
-    if mask is not None:
-        wgt = wgt * mask.repeat_interleave(4, dim=0).view(n * 4, h * w).float()
-    den = torch.zeros((n * 4, h * w), device=data.device).scatter_add(1, pos.long(), wgt)
-    den = den.view(n, 4, h, w).sum(1, keepdim=True)
-    acc = torch.zeros((n * 4 * c, h * w), device=data.device).scatter_add(
-        1, pos.repeat_interleave(c, dim=0).long(), wgt.repeat_interleave(c, dim=0) * data.repeat_interleave(4, dim=0).view(n * 4 * c, h * w))
-    return acc.view(n, 4, c, h, w).sum(1) / torch.clamp_min(den, 1e-3), den.squeeze(1)
 
 
 def _close(got, exp, what, rtol=case_runner.GRAD_RTOL):
