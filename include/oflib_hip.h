@@ -77,10 +77,6 @@ int ofl_version(void);
  *   All options are PROCESS-GLOBAL, unsynchronised testing / benchmarking aids: set them before any concurrent use of the
  *   library, never from two threads; production code leaves them alone. */
 #define OFL_OPT_SPLAT_FALLBACK_SLOTS 5
-/*   OFL_OPT_SPLAT_PATH: gather kernel of ofl_splat_tiled_f32 and its relatives: 0 = the round-6 kernel (16-24-byte records,
- *   one-word cells: three 512-thread blocks per CU), 1 = round 5's (32-byte records, two blocks per CU).  Same sums in the same
- *   order: bit-identical results (the tests compare them); speed only. */
-#define OFL_OPT_SPLAT_PATH 6
 /*   OFL_OPT_SPLAT_EXTRA_LDS: bytes of dynamic LDS added to the round-6 gather kernel's launches (0 = none) -- a measuring aid: it
  *   lowers the blocks a CU holds (28 672: two, 65 536: one) without changing a single instruction (tools/splat_occupancy.py). */
 #define OFL_OPT_SPLAT_EXTRA_LDS 7

@@ -34,8 +34,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP kernels + C ABI into oflibpytorch_amd/libofl_hip.so (cross-compiles without a GPU)."""
     if not force and not needs_build():
         return LIB_PATH
-    # the three translation units are compiled side by side (ofl_kernels.hip alone is ~80 s of device code generation: the splat
-    # gather kernel has 16 instantiations), then linked
+    # the translation units are compiled side by side (ofl_kernels.hip, the longest, is over a minute of device code generation; the
+    # gather splat's kernel and its instantiations compile in ofl_splat_gather.hip next to it), then linked
     import tempfile
     compile_flags = [f for f in HIPCC_FLAGS if f != "-shared"]
     # (the link line is derived from the same list: what is not a code-generation or language option of the compile step)

@@ -18,7 +18,7 @@ import torch
 from . import _build
 
 FLAG_NONFINITE, FLAG_NZ, FLAG_NZ_THR, FLAG_NZ_MASKED, FLAG_NZ_THR_MASKED = 1, 2, 4, 8, 16
-ABI_VERSION = 34              # ofl_version() of the library this file's argtypes describe
+ABI_VERSION = 35              # ofl_version() of the library this file's argtypes describe
 ROUND_NONE, ROUND_RINT, ROUND_U8 = 0, 1, 2
 THRESHOLD = 1e-3
 
@@ -579,12 +579,6 @@ def splat_tile_geometry() -> tuple:
     tw, th, cap = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
     _check(load_library().ofl_splat_tile_geometry(ctypes.byref(tw), ctypes.byref(th), ctypes.byref(cap)), "ofl_splat_tile_geometry")
     return tw.value, th.value, cap.value
-
-
-def set_splat_gather_kernel(which: int):
-    """Gather splat: 0 = the round-6 kernel (compact records, three blocks per CU; default), 1 = round 5's kernel.  The same sums
-    in the same order -- bit-identical results; tests compare the two, tools time them against each other."""
-    _check(load_library().ofl_set_option(6, int(which)), "ofl_set_option")
 
 
 def last_kernel_name(demangle: bool = True) -> str:

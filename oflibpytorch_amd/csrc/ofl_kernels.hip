@@ -152,12 +152,6 @@ struct WarpParamsLean : WarpParams { static constexpr bool kLean = true; };
 typedef const WarpParams __attribute__((address_space(4))) WarpParamsK;
 typedef const WarpParamsLean __attribute__((address_space(4))) WarpParamsLeanK;
 #define OFL_OPAQUE_S(ptr_) asm volatile("" : "+s"(ptr_))
-#ifndef OFL_WARP_KARG
-#define OFL_WARP_KARG 1
-#endif
-#ifndef OFL_WARP_COL_ADD
-#define OFL_WARP_COL_ADD 1
-#endif
 
 constexpr int kTileW = 64;   // one wavefront spans 64 consecutive x: 256-byte rows per instruction
 constexpr int kRows = 4;     // rows per thread (independent pixels in flight per lane)
@@ -197,9 +191,6 @@ __device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<con
 __device__ __forceinline__ f4 ld4nt(const float* p) { return __builtin_nontemporal_load(reinterpret_cast<const f4u*>(p)); }
 __device__ __forceinline__ f2 ld2(const float* p) { return *reinterpret_cast<const f2u*>(p); }
 __device__ __forceinline__ void st4(float* p, f4 v) { *reinterpret_cast<f4u*>(p) = v; }
-#ifndef OFL_WARP_NT_STORE
-#define OFL_WARP_NT_STORE 1      // 1: the warped channels, 2: the valid mask too (measured: 1 is +0.5..1 %, 2 loses 3 % -- its 32-byte pieces need the L2 to merge them)
-#endif
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p);
 __device__ __forceinline__ uint32_t ld16(const uint8_t* p);
 __device__ __forceinline__ void st32(uint8_t* p, uint32_t v);
@@ -226,27 +217,19 @@ __device__ __forceinline__ void st4(_Float16* p, f4 v) { *reinterpret_cast<h4u*>
 __device__ __forceinline__ void st2(_Float16* p, f2 v) { *reinterpret_cast<h2u*>(p) = (h2u){(_Float16)v[0], (_Float16)v[1]}; }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(_Float16* p, float v) { *p = (_Float16)v; }
-// write-once outputs of the staged warp: non-temporal (OFL_WARP_NT_STORE), so that they stream past the L2 lines the halos live
-// in; the gather splat's 16-byte output stores use it too (+1 % on smooth flows).  (Also measured, within +-1 %:
+// write-once outputs of the staged warp: non-temporal, so that they stream past the L2 lines the halos live in (+0.5 .. 1 %);
+// the gather splat's 16-byte output stores use it too (+1 % on smooth flows).  (Also measured, within +-1 %:
 // non-temporal flow-mask loads, non-temporal loads in the splat's bin kernel.)
 template <typename T> __device__ __forceinline__ void st4o(T* p, f4 v) { st4(p, v); }
-#if OFL_WARP_NT_STORE
 template <> __device__ __forceinline__ void st4o<float>(float* p, f4 v) { __builtin_nontemporal_store(v, reinterpret_cast<f4u*>(p)); }
-#endif
 template <typename T> __device__ __forceinline__ float stored_as(float v) { return v; }          // the value a store of type T keeps
 template <> __device__ __forceinline__ float stored_as<_Float16>(float v) { return (float)(_Float16)v; }
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return reinterpret_cast<const U32u*>(p)->v; }
 __device__ __forceinline__ uint32_t ld16(const uint8_t* p) { return reinterpret_cast<const U16u*>(p)->v; }
 __device__ __forceinline__ void st32(uint8_t* p, uint32_t v) { reinterpret_cast<U32u*>(p)->v = v; }
 __device__ __forceinline__ void st16(uint8_t* p, uint32_t v) { reinterpret_cast<U16u*>(p)->v = (uint16_t)v; }
-typedef uint32_t u32u __attribute__((aligned(1)));
-__device__ __forceinline__ void st32o(uint8_t* p, uint32_t v) {
-#if OFL_WARP_NT_STORE >= 2
-    __builtin_nontemporal_store(v, reinterpret_cast<u32u*>(p));
-#else
-    st32(p, v);
-#endif
-}
+// the valid mask's stores stay temporal (non-temporal ones lose 3 %: their 32-byte pieces need the L2 to merge them)
+__device__ __forceinline__ void st32o(uint8_t* p, uint32_t v) { st32(p, v); }
 // a 4-pixel group that starts `d` pixels after (width - 4), the last position a whole group fits in a row (widths that are
 // not multiples of 4): read that last whole group and rotate; the pixels past the row end are never used
 __device__ __forceinline__ f4 rot4(f4 v, int d) { return d == 1 ? (f4){v[1], v[2], v[3], v[3]} : d == 2 ? (f4){v[2], v[3], v[3], v[3]} : (f4){v[3], v[3], v[3], v[3]}; }
@@ -272,36 +255,6 @@ __device__ __forceinline__ f4 rot4(f4 v, int d) { return d == 1 ? (f4){v[1], v[2
 // A tile whose box does not fit the LDS budget gathers straight from global memory (same arithmetic).
 // Barriers order LDS traffic only (s_waitcnt lgkmcnt(0); s_barrier): global loads and stores stay in flight across them.
 // ------------------------------------------------------------------------------------------------
-#ifndef OFL_WARP_LEAN
-#define OFL_WARP_LEAN 1
-#endif
-#ifndef OFL_WARP_REUSE
-#define OFL_WARP_REUSE 1
-#endif
-#ifndef OFL_WARP_CHAN
-#define OFL_WARP_CHAN 1
-#endif
-#ifndef OFL_WARP_CHAN_WIDE
-#define OFL_WARP_CHAN_WIDE 1
-#endif
-#ifndef OFL_WARP_CHAN_SUBS
-#define OFL_WARP_CHAN_SUBS 1       // tiles side by side per block of the 64 x 16 channel-loop kernel.  3 (one 768-thread block per CU, its three tiles in lockstep so that they share their x-halo lines) was built and measured: bit-identical, 40 % SLOWER (profiles/r5_chan_pmc.txt) -- the lockstep that shares the lines also makes the whole CU wait together
-#endif
-#ifndef OFL_WARP_ALWAYS_T
-#define OFL_WARP_ALWAYS_T 1
-#endif
-#ifndef OFL_WARP_MERGE_BARRIER
-#define OFL_WARP_MERGE_BARRIER 1
-#endif
-#ifndef OFL_WARP_UNCOND_ROUNDS
-#define OFL_WARP_UNCOND_ROUNDS 1
-#endif
-#ifndef OFL_WARP_UNCOND_STORE
-#define OFL_WARP_UNCOND_STORE 1
-#endif
-#ifndef OFL_WARP_CLIP_COLUMN
-#define OFL_WARP_CLIP_COLUMN 1
-#endif
 #ifndef OFL_WARP_CLIP
 #define OFL_WARP_CLIP 8      // 0: an oversize box gathers the whole tile from global memory; n: stage its first rows if at least n fit
 #endif
@@ -315,9 +268,6 @@ __device__ __forceinline__ f4 rot4(f4 v, int d) { return d == 1 ? (f4){v[1], v[2
 #define OFL_LDS_BYTES 26624
 #endif
 constexpr int kLdsNT = OFL_LDS_NT, kLdsTWQ = OFL_LDS_TWQ, kLdsTH = kLdsNT / kLdsTWQ, kLdsIters = 3;
-#ifndef OFL_WARP_WIDE
-#define OFL_WARP_WIDE 1
-#endif
 #ifndef OFL_WARP_T
 #define OFL_WARP_T 4
 #endif
@@ -546,15 +496,15 @@ __device__ __forceinline__ void lds_issue(const WP& p, const TS* __restrict__ sb
 #pragma unroll
     for (int it = 0; it < kLdsIters; ++it) {
         S.slot[it] = -1;
-        // the first OFL_WARP_UNCOND_ROUNDS rounds are issued whatever the box (lanes past its last chunk re-read chunk 0 and
+        // the first round is issued whatever the box (lanes past its last chunk re-read chunk 0 and
         // write nothing to the LDS): loads in straight-line code are loads the compiler can COUNT, so the wait for the next
         // tile's flow (older than these loads) no longer waits for them too -- its coordinates are computed while they fly
-        if (it < OFL_WARP_UNCOND_ROUNDS || it < rounds) {
+        if (it == 0 || it < rounds) {
             const uint32_t i = (uint32_t)tid + it * kLdsNT;
             // 24-bit multiplies (full rate): i < 2^9, inv <= 2^20, rows and columns < 2^13, h * w < 2^24
             const uint32_t r = __umul24(i, inv) >> 20, c4 = i - __umul24(r, (uint32_t)B.cw);
             const int y = B.miny + (int)r + lds_shear(B.cbase + (int)c4, B.sq);
-            const bool on = (i < (uint32_t)B.nch) && ((uint32_t)y < (uint32_t)p.h) && (OFL_WARP_UNCOND_ROUNDS == 0 || it < rounds);
+            const bool on = (i < (uint32_t)B.nch) && ((uint32_t)y < (uint32_t)p.h) && it < rounds;
             const uint32_t g = on ? (uint32_t)(__mul24(y, p.w) + B.bx0) + c4 * 4u : 0u;
             S.slot[it] = on ? 1 + (int)(__umul24(r, (uint32_t)B.Pp) + c4) : -1;
             // the last chunk of a row of an image whose width is not a multiple of 4 would read past the row end (and past
@@ -567,9 +517,9 @@ __device__ __forceinline__ void lds_issue(const WP& p, const TS* __restrict__ sb
                 S.q[it][c] = ld4(sb + c * hw + ge);
                 if (SUB) S.q[it][c] = S.q[it][c] - ld4(sbb + c * hw + ge);     // (mode 1 't': the warped field is flow - self)
             }
-            // (OFL_WARP_UNCOND_ROUNDS, no target mask: the load reads the first plane's bytes and lds_write discards them -- still one countable load)
-            if (OFL_WARP_UNCOND_ROUNDS && VALID) S.mq[it] = ld32(sm ? sm + ge : reinterpret_cast<const uint8_t*>(sb) + ge);
-            else S.mq[it] = (VALID && sm) ? ld32(sm + ge) : 0x01010101u;
+            // (no target mask: the load reads the first plane's bytes and lds_write discards them -- still one countable load)
+            if (VALID) S.mq[it] = ld32(sm ? sm + ge : reinterpret_cast<const uint8_t*>(sb) + ge);
+            else S.mq[it] = 0x01010101u;
             if (wrem != 0) {
                 if (edge) {
 #pragma unroll
@@ -588,7 +538,7 @@ __device__ __forceinline__ void lds_write(f4* lds, const LdsBox& B, const LdsSta
 #pragma unroll
     for (int it = 0; it < kLdsIters; ++it) {
         if (S.slot[it] >= 0) {
-            const uint32_t mq = (OFL_WARP_UNCOND_ROUNDS && VALID && !has_sm) ? 0x01010101u : S.mq[it];
+            const uint32_t mq = (VALID && !has_sm) ? 0x01010101u : S.mq[it];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 f4 sl = {0.f, 0.f, 0.f, 0.f};
@@ -603,26 +553,11 @@ __device__ __forceinline__ void lds_write(f4* lds, const LdsBox& B, const LdsSta
 
 // ---- switches of the ROW-TABLE kernels (warp_bwd_rows_kernel and the ROWS instantiation of the channel loop, below; profiles/r5_warp_row_extents.txt)
 constexpr int kRowTab = 64;                    // rows of a tile's row table
-#ifndef OFL_ROWS_DEDUPE
-#define OFL_ROWS_DEDUPE 1     // neighbouring lanes with the same rows post once (DPP): -3 ... -6 % under smooth flows
-#endif
-#ifndef OFL_ROWS_PAD
-#define OFL_ROWS_PAD 0        // 1: rows padded to the rectangle's pitch rule -- measured slower everywhere (+2 ... 6 %: more LDS, no fewer conflicts -- the rows' own start columns already scatter them)
-#endif
 #ifndef OFL_ROWS_STAMPS
 #define OFL_ROWS_STAMPS 0     // 1: s_memtime stamps per phase, summed per block (tools/rows_stamps.py; never in a default build)
 #endif
-#ifndef OFL_WARP_ROWS_ADD
-#define OFL_WARP_ROWS_ADD 1   // mode 3 (the addend is the flow operand) on the row-table kernel
-#endif
 #ifndef OFL_ROWS_T
 #define OFL_ROWS_T 4          // tiles per column of large launches (2 and 3 measured: slower at B = 8 and at B = 64; 6 and 8, with an early exit below the frame: apply level, mode 3 +3 ... 5 % -- the prologue is not what is left)
-#endif
-#ifndef OFL_ROWS_ADD_REFORM
-#define OFL_ROWS_ADD_REFORM 0 // 1: mode 3 re-forms a tile's positions from the flow registers at gather time instead of keeping them (+6 % time)
-#endif
-#ifndef OFL_WARP_ROWS_FLOWOPS
-#define OFL_WARP_ROWS_FLOWOPS 1      // the other instantiations on row tables too: another addend (modes 1-2, Flow.combine), src - src_b staging (mode 1 't'), the output's flag word, fp16 / uint8 sources, the gradient with respect to the flow
 #endif
 #ifndef OFL_WARP_CHAN_WIDE_MIN
 #define OFL_WARP_CHAN_WIDE_MIN (2 * 6912u)      // 32 x 16 tiles of the launch from which the channel loop on the RECTANGLE runs on 64 x 16 tiles (with row extents: every size)
@@ -632,9 +567,6 @@ constexpr int kRowTab = 64;                    // rows of a tile's row table
 #endif
 #ifndef OFL_ROWS_T4_MIN
 #define OFL_ROWS_T4_MIN 5800u      // four-tile column groups (32-wide geometry) from which the row-table kernel runs four tiles per block (below: two / one)
-#endif
-#ifndef OFL_WARP_ROWS_SMALL
-#define OFL_WARP_ROWS_SMALL 1       // small plain launches and small mode 3 on the row-table kernel too (1 or 2 tiles per block)
 #endif
 
 // step 4a: gather from LDS (or from global memory when the box did not fit) and blend; per pixel (c0, c1, c2, mask channel)
@@ -800,39 +732,36 @@ __device__ __forceinline__ void lds_store(const WP& p, int tx, int ty, int n, ui
     const int tid = threadIdx.x, lx = tid % kLdsTWQ, ly = tid / kLdsTWQ;
     const int w = p.w, h = p.h;
     const int x4 = tx * (kLdsTWQ * 4) + lx * 4, y = ty * kLdsTH + ly;
-    // OFL_WARP_UNCOND_STORE: lanes past the frame's right / bottom edge have computed the CLAMPED pixel group (same flow, same
-    // coordinates, same taps as its owner) and store it again -- identical duplicate stores, as for the group that straddles a
-    // row end.  What it buys is not the branch: with the stores in straight-line code the compiler can COUNT them, so the next
-    // tile's wait for its flow / staged box becomes s_waitcnt vmcnt(4) instead of vmcnt(0), which also waited for these stores'
-    // acknowledgements (the vmcnt queue is in order) -- once per tile, with nothing else of the block in flight.
-    const bool inb = OFL_WARP_UNCOND_STORE || ((x4 < w) && (y < h));
+    // Lanes past the frame's right / bottom edge have computed the CLAMPED pixel group (same flow, same coordinates, same taps
+    // as its owner) and store it again -- identical duplicate stores, as for the group that straddles a row end.  What it buys
+    // is not the branch: with the stores in straight-line code the compiler can COUNT them, so the next tile's wait for its flow /
+    // staged box becomes s_waitcnt vmcnt(4) instead of vmcnt(0), which also waited for these stores' acknowledgements (the vmcnt
+    // queue is in order) -- once per tile, with nothing else of the block in flight.
     const uint32_t pix = (uint32_t)(min(y, h - 1) * w + min(x4, w - 4));
-    if (inb) {
-        uint32_t vo = 0x01010101u;
-        if (VALID) {
-            vo = 0;
+    uint32_t vo = 0x01010101u;
+    if (VALID) {
+        vo = 0;
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                vo |= (uint32_t)((outv[k][3] > kValidThr) && (((fmask4 >> (8 * k)) & 0xffu) != 0u)) << (8 * k);
-            st32o(p.valid + (int64_t)n * hw + pix, vo);
+        for (int k = 0; k < 4; ++k)
+            vo |= (uint32_t)((outv[k][3] > kValidThr) && (((fmask4 >> (8 * k)) & 0xffu) != 0u)) << (8 * k);
+        st32o(p.valid + (int64_t)n * hw + pix, vo);
+    }
+    TD* __restrict__ db = reinterpret_cast<TD*>(p.dst) + (int64_t)n * p.dst_bs + choff;   // (choff: first plane of a channel group, warp_bwd_lds_chan_kernel)
+    f4 o01[2];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        f4 o = {outv[0][c], outv[1][c], outv[2][c], outv[3][c]};
+        if (ADD) o = addend[c] * p.a_sign + o * p.g_sign;
+        if (OFL_WP_ROUND(p) != OFL_ROUND_NONE) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = apply_round(o[k], OFL_WP_ROUND(p));
         }
-        TD* __restrict__ db = reinterpret_cast<TD*>(p.dst) + (int64_t)n * p.dst_bs + choff;   // (choff: first plane of a channel group, warp_bwd_lds_chan_kernel)
-        f4 o01[2];
+        st4o(db + c * hw + pix, o);
+        if (DF && c < 2) o01[c] = o;
+    }
+    if (DF && NC == 2) {                               // flag word of the OUTPUT read as a flow under `valid` (by-product)
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            f4 o = {outv[0][c], outv[1][c], outv[2][c], outv[3][c]};
-            if (ADD) o = addend[c] * p.a_sign + o * p.g_sign;
-            if (OFL_WP_ROUND(p) != OFL_ROUND_NONE) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) o[k] = apply_round(o[k], OFL_WP_ROUND(p));
-            }
-            st4o(db + c * hw + pix, o);
-            if (DF && c < 2) o01[c] = o;
-        }
-        if (DF && NC == 2) {                               // flag word of the OUTPUT read as a flow under `valid` (by-product)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) *dflags |= flag_bits(o01[0][k], o01[NC - 1][k], ((vo >> (8 * k)) & 0xffu) != 0u);
-        }
+        for (int k = 0; k < 4; ++k) *dflags |= flag_bits(o01[0][k], o01[NC - 1][k], ((vo >> (8 * k)) & 0xffu) != 0u);
     }
 }
 
@@ -844,9 +773,8 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_lds_kernel(const WarpParam
     int tx, ty2, n;                      // the grid counts tile PAIRS: tiles_y = ceil(h / (2 * kLdsTH))
     if (!decode_tile(p, tx, ty2, n)) return;
     const int tyA = 2 * ty2, tyB = tyA + 1;
-    // (OFL_WARP_ALWAYS_T: the second tile is run whatever the frame's height -- past the bottom edge it recomputes and re-stores the
-    // last row, see the column kernel -- so that its staging loads and both tiles' stores are straight-line code the compiler counts)
-    const bool haveB = OFL_WARP_ALWAYS_T || tyB * kLdsTH < p.h;
+    // (the second tile is run whatever the frame's height -- past the bottom edge it recomputes and re-stores the last row, see the
+    // column kernel -- so that its staging loads and both tiles' stores are straight-line code the compiler counts)
     const int tid = threadIdx.x, lx = tid % kLdsTWQ, ly = tid / kLdsTWQ;
     const int w = p.w, h = p.h;
     const uint32_t hw = (uint32_t)(h * w);
@@ -884,17 +812,11 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_lds_kernel(const WarpParam
     lds_coords_box(p, tx, tyA, uA, vA, sq, TA, BA, red[0]);
     lds_issue<NC, VALID, SUB, TS>(p, sb, sm, hw, BA, S, sbb);   // staging loads of A fly ...
     // ... while B's coordinates are computed; the block-wide half of B's box waits for the barrier that publishes A's staged box
-    // (OFL_WARP_MERGE_BARRIER: one barrier per tile fewer)
-#if OFL_WARP_MERGE_BARRIER
+    // (one barrier per tile fewer)
     const LdsBoxWords wB = lds_coords_box_a(p, tx, tyB, uB, vB, sq, TB, red[1]);
-#else
-    lds_coords_box(p, tx, tyB, uB, vB, sq, TB, BB, red[1]);
-#endif
     lds_write<NC, VALID>(lds, BA, S, sm != nullptr);
     lds_barrier();
-#if OFL_WARP_MERGE_BARRIER
     lds_coords_box_b(p, sq, wB, BB, red[1]);
-#endif
     // the vmcnt queue is in order: the addend (an L2 hit when it is the flow itself) is fetched BEFORE B's staging loads /
     // A's stores, so that waiting for it never waits for them
     // (flows only: with three channels the extra registers would spill, and nothing on the host adds to an image)
@@ -902,16 +824,12 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_lds_kernel(const WarpParam
     f4 outv[4], aA[NC], aB[NC];
     const bool reuse = EARLY && NC == 2 && p.add_is_flow;         // block-uniform
     if (EARLY) { if (reuse) { aA[0] = uA; aA[NC - 1] = vA; } else lds_load_addend<NC>(p, tx, tyA, n, hw, aA); }
-    if (haveB) lds_issue<NC, VALID, SUB, TS>(p, sb, sm, hw, BB, S, sbb);   // staging loads of B fly while A is gathered and stored
+    lds_issue<NC, VALID, SUB, TS>(p, sb, sm, hw, BB, S, sbb);   // staging loads of B fly while A is gathered and stored
     lds_gather<NC, VALID, SUB, TS>(p, hw, sb, sm, TA, BA, smem, outv, sbb);
-    if (EARLY && haveB) { if (reuse) { aB[0] = uB; aB[NC - 1] = vB; } else lds_load_addend<NC>(p, tx, tyB, n, hw, aB); }
+    if (EARLY) { if (reuse) { aB[0] = uB; aB[NC - 1] = vB; } else lds_load_addend<NC>(p, tx, tyB, n, hw, aB); }
     if (ADD && !EARLY) lds_load_addend<NC>(p, tx, tyA, n, hw, aA);
     int dflags = 0;
     lds_store<NC, VALID, ADD, DF, TD>(p, tx, tyA, n, hw, fmA, outv, aA, &dflags);
-    if (!haveB) {
-        if (DF) { dflags = wave_or_flags(dflags); if ((tid & 63) == 0) flag_or(&p.dst_flags[n], dflags); }
-        return;
-    }
     lds_barrier();
     lds_write<NC, VALID>(lds, BB, S, sm != nullptr);
     lds_barrier();
@@ -935,19 +853,13 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_lds_kernel(const WarpParam
 template <int T, int NC, bool VALID, bool ADD, bool DF = false, bool SUB = false, typename TS = float, typename TD = float, bool GRAD = false, bool REUSE = false, bool LEAN = false>
 __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_lds_column_kernel(const WarpParams p_by_value) {
     static_assert(!REUSE || (ADD && NC == 2 && !GRAD), "REUSE: the fused composition");
-#if OFL_WARP_KARG
     // parameters through the kernarg segment (see OFL_OPAQUE_S at the gather splat): the ~250 bytes of WarpParams are not
     // held in SGPRs (and spilled to VGPR lanes) across the whole column, each phase s_loads what it needs
     typedef typename std::conditional<LEAN, WarpParamsLeanK, WarpParamsK>::type WPK;       // (LEAN: see WarpParamsLean)
     WPK* pp = (WPK*)__builtin_amdgcn_kernarg_segment_ptr();
 #define p (*pp)
-#define OFL_WARP_PHASE() OFL_OPAQUE_S(pp)
-#else
-    const WarpParams& p = p_by_value;
-#define OFL_WARP_PHASE()
-#endif
     constexpr int NW = kLdsNT / 64;
-    constexpr bool kClip = OFL_WARP_CLIP_COLUMN && T > 1;   // oversize boxes: stage the rows that fit (lds_coords_box); not in the one-tile kernel of tiny launches (+2 % there)
+    constexpr bool kClip = T > 1;   // oversize boxes: stage the rows that fit (lds_coords_box); not in the one-tile kernel of tiny launches (+2 % there)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int red[2][NW][4];
     int tx, tyg, n;                      // the grid counts tile GROUPS: tiles_y = ceil(h / (T * kLdsTH))
@@ -969,11 +881,11 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_lds_column_kernel(const Wa
         const uint32_t pix = (uint32_t)(min((tyg * T + k) * kLdsTH + ly, h - 1) * w + xq);
         uu[k] = ld4nt(fu + pix); vv[k] = ld4nt(fu + hw + pix);
         fmk[k] = 0x01010101u;
-        // (OFL_WARP_UNCOND_ROUNDS: countable, as the staging loads: no flow mask -> a read of the flow's bytes, discarded where the word is used)
-        if (OFL_WARP_UNCOND_ROUNDS && VALID) fmk[k] = ld32(fm ? fm + pix : reinterpret_cast<const uint8_t*>(fu) + pix);
-        else if ((VALID || OFL_WP_FLOW_FLAGS(p)) && fm) fmk[k] = ld32(fm + pix);
+        // (countable, as the staging loads: no flow mask -> a read of the flow's bytes, discarded where the word is used)
+        if (VALID) fmk[k] = ld32(fm ? fm + pix : reinterpret_cast<const uint8_t*>(fu) + pix);
+        else if (OFL_WP_FLOW_FLAGS(p) && fm) fmk[k] = ld32(fm + pix);
     };
-    auto fmw = [&](int k) -> uint32_t { return (OFL_WARP_UNCOND_ROUNDS && VALID && !fm) ? 0x01010101u : fmk[k]; };
+    auto fmw = [&](int k) -> uint32_t { return (VALID && !fm) ? 0x01010101u : fmk[k]; };
     auto note_flags = [&](int k) {       // finiteness / zero tests of the flow operand as a by-product (wave-uniform branch)
         if (OFL_WP_FLOW_FLAGS(p) && (x4 < w) && ((tyg * T + k) * kLdsTH + ly < h)) {
 #pragma unroll
@@ -1002,30 +914,24 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_lds_column_kernel(const Wa
     int dflags = 0;
 #pragma unroll
     for (int k = 0; k < T; ++k) {
-        OFL_WARP_PHASE();
+        OFL_OPAQUE_S(pp);
         const int tyk = tyg * T + k;
-        // OFL_WARP_ALWAYS_T: a block runs all T tiles of its column whatever the frame's height -- a tile past the bottom edge
+        // A block runs all T tiles of its column whatever the frame's height -- a tile past the bottom edge
         // recomputes and re-stores the frame's last row (clamped loads, identical duplicate stores), at most T - 1 tiles of
         // the last row of groups.  No run-time branch round the staging loads or the stores is left, so the compiler counts
         // every one of them in its vmcnt waits (see lds_store).
         // (not with the ADD epilogue: its re-used flow registers leave no room for the longer live ranges -- 36 B of scratch, -13 %)
-        const bool more = (k + 1 < T) && ((OFL_WARP_ALWAYS_T && (!ADD || (REUSE && OFL_WARP_ALWAYS_T >= 2))) || (tyk + 1) * kLdsTH < h);        // block-uniform: a tile follows
+        const bool more = (k + 1 < T) && (!ADD || (tyk + 1) * kLdsTH < h);        // block-uniform: a tile follows
         LdsBoxWords wn = {0, 0};
         if (k + 1 < T) {
-            // ... while the next tile's coordinates are computed (OFL_WARP_MERGE_BARRIER: the block-wide half of its box behind the
-            // barrier that publishes this tile's staged box -- one barrier per tile fewer)
-#if OFL_WARP_MERGE_BARRIER
+            // ... while the next tile's coordinates are computed (the block-wide half of its box behind the barrier that publishes
+            // this tile's staged box -- one barrier per tile fewer)
             if (more) { note_flags(k + 1); wn = lds_coords_box_a(p, tx, tyk + 1, uu[k + 1], vv[k + 1], sq[k + 1], Tc[REUSE ? 0 : k + 1], red[(k + 1) & 1]); }
-#else
-            if (more) { note_flags(k + 1); lds_coords_box<true, kClip>(p, tx, tyk + 1, uu[k + 1], vv[k + 1], sq[k + 1], Tc[REUSE ? 0 : k + 1], Bx[k + 1], red[(k + 1) & 1]); }
-#endif
         }
         if (k + 2 < T) load_flow(k + 2);
         lds_write<NC, VALID>(lds, Bx[k], S, sm != nullptr);
         lds_barrier();
-#if OFL_WARP_MERGE_BARRIER
         if (k + 1 < T) { if (more) lds_coords_box_b<kClip>(p, sq[k + 1], wn, Bx[k + 1], red[(k + 1) & 1]); }
-#endif
         f4 outv[4], ad[NC];
         if (EARLY) { if (reuse) { ad[0] = uu[k]; ad[NC - 1] = vv[k]; } else lds_load_addend<NC>(p, tx, tyk, n, hw, ad); }
         if (GRAD) lds_load_addend<NC>(p, tx, tyk, n, hw, ad);              // the upstream gradient of the tile, ahead of the younger loads
@@ -1051,13 +957,10 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_lds_column_kernel(const Wa
         if ((tid & 63) == 0) flag_or(&p.flow_flags[n], fflags);
     }
     if (DF) { dflags = wave_or_flags(dflags); if ((tid & 63) == 0) flag_or(&p.dst_flags[n], dflags); }
-#undef OFL_WARP_PHASE
-#if OFL_WARP_KARG
 #undef p
-#endif
 }
 
-// ROW TABLES (OFL_WARP_ROWS; VERDICT r4 item 2: "per-row extents of the staged box"; profiles/r5_warp_row_extents.txt).  The column
+// ROW TABLES ("per-row extents of the staged box"; profiles/r5_warp_row_extents.txt).  The column
 // kernel above stages ONE y-sheared rectangle per tile; under the bench flow (sigma 8) it holds 1.65 source pixels per output pixel of a
 // 64 x 16 tile, and a rougher flow overflows it (10.8 % of the tiles at sigma 12, 27.5 % at sigma 16).  Here every source ROW the tile
 // touches has its own first chunk and length, the rows packed back to back in LDS (tools/box_rows_model_wide3.py: 1.27 staged pixels per
@@ -1079,9 +982,6 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_lds_column_kernel(const Wa
 // Same expressions per pixel as the column kernel: bit-identical.  64 x 16 tiles (ofl_warp_wide.hip); launches with W % 4 == 0 and no
 // flow-flag by-product: four tiles per block for large ones, one or two for small ones (ofl_wide_launch_column / _rows_small / _rows_h /
 // _rows_u8 / _rows_grad, and the channel loop's ROWS instantiation).
-#ifndef OFL_WARP_ROWS
-#define OFL_WARP_ROWS 1
-#endif
 constexpr int kRowChunks = kLdsIters * kLdsNT - 16;             // chunks (4 pixels, one 16-byte slot each) a block stages per tile (3 blocks per CU: 53.3 KB with the tables below)
 constexpr int kRowsLdsBytes = 16 * (2 + 4 * kRowChunks);        // slot 0 (zeros: invalid taps) + the packed rows + a spare slot (rows_extra)
 static_assert(kRowChunks % 4 == 0, "clear_starts zeroes the chunk map a dword at a time");
@@ -1090,7 +990,6 @@ constexpr int kRowMargin = 8;
 struct RowTabs { int tmin[2][kRowTab + 1]; int tmax[2][kRowTab + 1]; uint32_t ent[2][kRowTab]; uint8_t start[2][kRowChunks]; };   // ([kRowTab]: "a post was dropped"; start[i]: 1 + the row whose first chunk is chunk i, else 0)
 struct RowGeo { int org, cxo, tot; bool interior; };            // wave-uniform
 struct RowScan { int incl, sc, a; };                         // lane = row: chunks up to and including this row; the same | padded chunks << 16; first chunk | length << 16
-__device__ __forceinline__ int rows_pitch(int cw) { return OFL_ROWS_PAD ? (cw ? lds_pitch(4 * cw) >> 2 : 0) : cw; }   // LDS chunks (4 slots) a row of cw chunks occupies
 
 __device__ __forceinline__ int wave_incl_scan(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);    // row_shr:1
@@ -1153,14 +1052,10 @@ __device__ __forceinline__ void rows_post(const WP& p, const LdsCoords& T, int o
     // huge value -- walks 64 rows at most, and the packed compare below cannot alias)
     const bool drop = a < 0 || b >= kRowTab;
     const int a0 = max(a, 0), b0 = min(b, kRowTab - 1);
-#if OFL_ROWS_DEDUPE
     const int ab = a0 | (b0 << 16);
     const int abl = __builtin_amdgcn_update_dpp(-1, ab, 0x111, 0xf, 0xf, false), cml = __builtin_amdgcn_update_dpp(0x7fffffff, cmin, 0x111, 0xf, 0xf, false);     // row_shr:1 (old: no neighbour)
     const int abr = __builtin_amdgcn_update_dpp(-1, ab, 0x101, 0xf, 0xf, false), cxr = __builtin_amdgcn_update_dpp(-0x7fffffff, cmax, 0x101, 0xf, 0xf, false);    // row_shl:1
     const bool pmin = !(abl == ab && cml <= cmin), pmax = !(abr == ab && cxr >= cmax);     // (the SAME rows: one compare, and what a smooth flow produces)
-#else
-    const bool pmin = true, pmax = true;
-#endif
 #pragma unroll
     for (int j = 0; j < 2; ++j) {          // (a lane touches at least two rows)
         const int r = a0 + j;
@@ -1185,17 +1080,17 @@ __device__ __forceinline__ void rows_scan(const WP& p, const int* tmin, const in
     const bool any = mx >= mn, inimg = (uint32_t)rowy < (uint32_t)p.h;
     const bool valid = any && c1 >= c0 && inimg;
     const int cw = valid ? c1 - c0 + 1 : 0;
-    // two sums in one scan: chunks (low half: chunk i -> thread i) and chunks of LDS the rows occupy (high half; the same unless
-    // OFL_ROWS_PAD pads a row to the rectangle's pitch rule, rows_pitch)
+    // two sums in one scan: chunks (low half: chunk i -> thread i) and chunks of LDS the rows occupy (high half; the same: rows are
+    // packed unpadded -- padded to the rectangle's pitch rule they measured +2 ... 6 %, more LDS and no fewer conflicts)
     const int cwc = min(cw, 1000);                                   // (a row that long is not staged; clamped, the 64 sums fit 16 bits)
-    const uint32_t sc = (uint32_t)wave_incl_scan(cwc | (rows_pitch(cwc) << 16));
+    const uint32_t sc = (uint32_t)wave_incl_scan(cwc | (cwc << 16));
     const int incl = (int)(sc & 0xffffu), pincl = (int)(sc >> 16);
     const int d = c0 - cxo;
     const bool fit = incl <= kRowChunks && pincl <= kRowChunks;      // (both sums are monotonic: the rows that fit are a prefix)
     const bool stg = valid && fit && (uint32_t)(d + 128) <= 256u;
     const int nst = __popcll(__ballot(fit));
     G.tot = nst ? __builtin_amdgcn_readlane(incl, nst - 1) : 0;
-    const uint32_t e = stg ? ((uint32_t)(16 * (1 + 4 * (pincl - rows_pitch(cwc)) - d + 256)) | ((uint32_t)(16 * cw) << 16)) : ((any && !valid) ? 1u : 0u);
+    const uint32_t e = stg ? ((uint32_t)(16 * (1 + 4 * (pincl - cwc) - d + 256)) | ((uint32_t)(16 * cw) << 16)) : ((any && !valid) ? 1u : 0u);
     const bool outside = any && (mn < 0 || mx > (p.w >> 2) - 1 || !inimg);      // a tap outside the frame (or in its last, partial chunk)
     G.interior = (ov <= 0) && (__ballot((valid && !stg) || outside) == 0ull) && G.tot > 0;
     if (ENT && threadIdx.x < 64) ent[l] = e;
@@ -1226,7 +1121,7 @@ __device__ __forceinline__ void rows_map(const WP& p, const RowGeo& G, const Row
     const int row = max(wave_incl_max((int)start[min(i, kRowChunks - 1)]), carry) - 1;
     const int rowc = min(row, kRowTab - 1);
     const int ra = __builtin_amdgcn_ds_bpermute(rowc << 2, R.a), rs = __builtin_amdgcn_ds_bpermute(rowc << 2, R.sc);
-    const int cwr = ra >> 16, c0 = ra & 0xffff, cl = i - ((rs & 0xffff) - cwr), pb = (int)((uint32_t)rs >> 16) - rows_pitch(cwr);
+    const int cwr = ra >> 16, c0 = ra & 0xffff, cl = i - ((rs & 0xffff) - cwr), pb = (int)((uint32_t)rs >> 16) - cwr;
     const bool on = i < G.tot;
     g = on ? (uint32_t)(__mul24(G.org + rowc, p.w) + ((c0 + cl) << 2)) : 0u;
     slot = on ? ((1 + 4 * pb + cl) | (cwr << 16)) : -1;
@@ -1244,7 +1139,7 @@ __device__ __forceinline__ void rows_issue(const WP& p, const TS* __restrict__ s
     for (int it = 0; it < kRowIters; ++it) {
         S.slot[it] = -1;
         const int i0 = it * kLdsNT + wv * 64;
-        if (it < OFL_WARP_UNCOND_ROUNDS || i0 < G.tot) {       // (the first round whatever the tile: countable loads, see lds_issue)
+        if (it == 0 || i0 < G.tot) {       // (the first round whatever the tile: countable loads, see lds_issue)
             uint32_t g;
             rows_map(p, G, R, start, i0, g, S.slot[it]);
 #pragma unroll
@@ -1375,7 +1270,7 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_rows_kernel(const WarpPara
     f4* lds = reinterpret_cast<f4*>(smem);
     // mode 3: a tile's positions are KEPT from the posts to the gather (-6 % against re-forming them from the flow registers) -- except with
     // the flag by-product, where the kept positions spill (32 B of scratch)
-    constexpr bool REFORM = ADD == 1 && (OFL_ROWS_ADD_REFORM || DF);
+    constexpr bool REFORM = ADD == 1 && DF;
     LdsCoords Tc[REFORM ? 1 : T];
     RowGeo Gx[T];
     RowStage<NC> S;
@@ -1396,7 +1291,7 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_rows_kernel(const WarpPara
 #pragma unroll
     for (int k = 0; k < T; ++k) {
         OFL_OPAQUE_S(pp);
-        const int tyk = tyg * T + k;       // (a tile past the bottom edge recomputes and re-stores the frame's last row: OFL_WARP_ALWAYS_T)
+        const int tyk = tyg * T + k;       // (a tile past the bottom edge recomputes and re-stores the frame's last row, see the column kernel)
         if (k + 1 < T) {
             lds_coords_box_a<false>(p, tx, tyk + 1, uu[k + 1], vv[k + 1], 0, Tc[REFORM ? 0 : k + 1], (int (*)[4])nullptr);
             OFL_RS(1);
@@ -1512,7 +1407,9 @@ __device__ __attribute__((noinline)) Out4 chan_pixels_from_global(WarpParamsK* p
 // walking the channel groups in LOCKSTEP (the barriers are the block's).  What it buys: the x-halo of neighbouring boxes -- partial 128-byte
 // lines that a lone tile fetches for itself, per group, because its neighbours are at other groups at that moment (profiles/r5_chan_pmc.txt)
 // -- is requested by waves of ONE CU within the same few hundred cycles and fetched once.  The grid then counts tile TRIPLES along x; a
-// sub-tile past the frame's right edge recomputes the last columns (clamped loads, identical duplicate stores).
+// sub-tile past the frame's right edge recomputes the last columns (clamped loads, identical duplicate stores).  Measured with 3 (one
+// 768-thread block per CU): bit-identical, 40 % SLOWER -- the lockstep that shares the lines also makes the whole CU wait together; the
+// launchers use 1.
 // ROWS: per-row extents of the staged box (see warp_bwd_rows_kernel) -- table, scan, chunk map and tap addresses are formed ONCE per
 // tile like every other invariant, so the channel loop is unchanged and every group stages ~23 % fewer bytes at sigma 8.
 template <typename WP>
@@ -2207,12 +2104,6 @@ __global__ __launch_bounds__(256) void splat_fallback_kernel(const SplatParams p
 //  subtiles spread over > 256 destination tiles takes the two-pass global-atomics path inside the same call, decided on
 //  the device, per image.
 // ------------------------------------------------------------------------------------------------
-#ifndef OFL_SP_LEAN
-#define OFL_SP_LEAN 1
-#endif
-#ifndef OFL_SP_ISSUE_FIRST
-#define OFL_SP_ISSUE_FIRST 1
-#endif
 #ifndef OFL_SP_TW
 #define OFL_SP_TW 64    // width of a destination tile (32: 256-thread blocks, 4 per CU; 64: 512-thread blocks, 2 per CU -- fewer source pixels scanned per output pixel and half the per-tile prologues; round 3: 32 by 1 %, round 4 after the long cells left the critical path: 64 by 4 % at sigma 8, 30 % at B = 1)
 #endif
@@ -2222,10 +2113,6 @@ __global__ __launch_bounds__(256) void splat_fallback_kernel(const SplatParams p
 constexpr int kSpTW = OFL_SP_TW, kSpTH = OFL_SP_TH;          // destination tiles
 static_assert(kSpTW == 32 || kSpTW == 64, "destination tile width");
 constexpr int kSpNT2 = kSpTW * kSpTH / 2;                    // gather kernel: 2 destination pixels per thread
-#ifndef OFL_SP_Q
-#define OFL_SP_Q (kSpTW == 32 ? 896 : 1792)    // (32-wide tiles: 1024 leaves room for 3 blocks per CU only; 896: 39.7 KB per block, 4 blocks -- measured -4 % / -13 % on apply 's' / switch_ref)
-#endif
-constexpr int kSpQ = OFL_SP_Q;                               // records the gather kernel holds in LDS at a time
 #ifndef OFL_SP_SUBH
 #define OFL_SP_SUBH 2
 #endif
@@ -2403,9 +2290,6 @@ __device__ __forceinline__ int row_pk_max_dpp(int v) {
     return kSubLanes == 16 ? pk_max16(v, OFL_DPPU(v, 0x140)) : v;
 }
 
-#ifndef OFL_BIN_SMALLDIV
-#define OFL_BIN_SMALLDIV 1
-#endif
 constexpr int kBinLocal = 64;   // destination tiles one 64 x 16 source region aggregates in LDS (more: straight to the global counters)
 
 // image n leaves the gather path (a list overflowed / a subtile is torn over the frame): its flag, and the statistics of
@@ -2508,7 +2392,7 @@ __global__ __launch_bounds__(256) void splat_bin_kernel(const GatherParams p) {
         lt[g] = -1; rank[g] = 0;
         fast[g] = local && cnt[g] <= kSubLanes;
         if (fast[g] && j0 < cnt[g]) {
-            const int jy = OFL_BIN_SMALLDIV ? small_div(j0, ntx[g]) : j0 / ntx[g];
+            const int jy = small_div(j0, ntx[g]);
             lt[g] = (ty0[g] + jy - bty0) * bntx + (tx0[g] + (j0 - jy * ntx[g]) - btx0);
             rank[g] = atomicAdd(&lcount[lt[g]], 1);
         }
@@ -2516,7 +2400,7 @@ __global__ __launch_bounds__(256) void splat_bin_kernel(const GatherParams p) {
     if (local) {
         __syncthreads();
         if (tid < bnt && lcount[tid] > 0) {
-            const int ly_ = OFL_BIN_SMALLDIV ? small_div(tid, bntx) : tid / bntx;
+            const int ly_ = small_div(tid, bntx);
             const int64_t d = (int64_t)n * p.tiles_img + (bty0 + ly_) * p.tiles_x + btx0 + (tid - ly_ * bntx);
             const int start = atomicAdd(&p.cnt[d], lcount[tid]);
             lbase[tid] = start;
@@ -2526,7 +2410,7 @@ __global__ __launch_bounds__(256) void splat_bin_kernel(const GatherParams p) {
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             if (lt[g] >= 0) {
-                const int ly_ = OFL_BIN_SMALLDIV ? small_div(lt[g], bntx) : lt[g] / bntx;
+                const int ly_ = small_div(lt[g], bntx);
                 const int64_t d = (int64_t)n * p.tiles_img + (bty0 + ly_) * p.tiles_x + btx0 + (lt[g] - ly_ * bntx);
                 const int pos = lbase[lt[g]] + rank[g];
                 if (pos < kBinCap) p.list[d * kBinCap + pos] = subid[g];
@@ -2556,113 +2440,6 @@ __device__ __forceinline__ void sp_corners(float xv, float yv, float wmax, float
     wx[0] = (x1 - xv) * (x0 == x0s ? 1.0f : 0.0f); wx[1] = (xv - x0) * (x1 == x1s ? 1.0f : 0.0f);
     wy[0] = (y1 - yv) * (y0 == y0s ? 1.0f : 0.0f); wy[1] = (yv - y0) * (y1 == y1s ? 1.0f : 0.0f);
     ix[0] = (int)x0s - dx0; ix[1] = (int)x1s - dx0; iy[0] = (int)y0s - dy0; iy[1] = (int)y1s - dy0;
-}
-
-#ifndef OFL_SP_MINB
-#define OFL_SP_MINB 4   // waves per SIMD the gather kernel's register budget is sized for (4 blocks of 256 threads / 2 of 512 per CU: what its LDS allows)
-#endif
-#ifndef OFL_SP_U
-#define OFL_SP_U 1      // list entries (subtiles) per thread and step of the gather kernel's walk
-#endif
-constexpr int kSpU = OFL_SP_U;
-// A RECORD is 32 bytes of LDS: the four corner weights w[ky][kx] = wy[ky] * wx[kx] of its end point -- wx = (x1 - x, x - x0),
-// wy alike, each product formed once, exactly as the reference's outer product (utils.py:1110-1114; a corner that a
-// destination pixel of the image reads is never clamped, so the `eq` factor is 1) -- then up to 3 data values and the key
-// (raster position of the source pixel, mask-channel bit below it).  Two ds_read_b128 bring a record.
-//
-// One record of the cell whose column is DC (-1, 0, +1) cells from the pair's middle cell and whose row serves corner
-// row KY, added to the sums of the destination pixels that read it: pixel 0 of the pair as its x-corner 1 (DC = -1) or
-// 0 (DC = 0), pixel 1 as its x-corner 1 (DC = 0) or 0 (DC = +1).  Product rounded, then added.
-template <int NC, int NCH, int DC, int KY>
-__device__ __forceinline__ void sp_use(const f4* rec4, uint32_t i, float (&a)[2][2][1 + NCH]) {
-    const f4 wv = rec4[2 * i], dv = rec4[2 * i + 1];
-    float d[NCH];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) d[c] = dv[c];
-    if (NCH > NC) d[NC] = (float)(__float_as_uint(dv[3]) & 1u);          // the mask channel rides in the key
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int kx = k - DC;                     // pixel k sits DC .. DC + 1 columns right of the cell: x-corner k - DC
-        if (kx < 0 || kx > 1) continue;
-        const float wgt = wv[KY * 2 + kx];
-        a[k][kx][0] += wgt;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) a[k][kx][1 + c] += wgt * d[c];
-    }
-}
-
-// A cell that phase S has already summed (more than two records): its class sums lie where its first three records were,
-// one f4 per channel (density, data ..., mask) holding the four corner classes in the order of a record's weights.
-template <int NCH, int DC, int KY>
-__device__ __forceinline__ void sp_use_presum(const f4* rec4, uint32_t ia, uint32_t ib, uint32_t ic, float (&a)[2][2][1 + NCH]) {
-#pragma unroll
-    for (int c = 0; c < 1 + NCH; ++c) {
-        const f4 pv = c < 2 ? rec4[2 * ia + c] : c < 4 ? rec4[2 * ib + (c - 2)] : rec4[2 * ic];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int kx = k - DC;
-            if (kx < 0 || kx > 1) continue;
-            a[k][kx][c] += pv[KY * 2 + kx];
-        }
-    }
-}
-
-#ifndef OFL_SP_LANEMAX
-#define OFL_SP_LANEMAX 12
-#endif
-#ifndef OFL_SP_NET8
-#define OFL_SP_NET8 1     // cells of five to N records are ordered by a sorting network in registers (1: N by channel count; 6 / 8: forced; 0: insertion sort up to OFL_SP_LANEMAX)
-#endif
-constexpr int kSpLaneMax = OFL_SP_LANEMAX;   // longest cell ONE lane puts in raster order (insertion on its chain); longer ones (up to kSpLong) are a wave's
-
-// A cell with kSpLaneMax < cn <= 64 records, ordered and summed by the 64 lanes of one wave (every lane of the wave calls this
-// with the same cell).  Leaves what the single-lane path leaves: the four class sums of every channel in the cell's first
-// three records (raster order) and the kLongCell marker in its slots.
-template <int NC, int NCH>
-__device__ __attribute__((noinline)) void sp_order_big_cell(unsigned char* raw, const uint32_t* ccnt, uint2* slots, const uint32_t* ohead,
-                                                  const uint16_t* link, int c, int lane) {
-    constexpr uint32_t kEnd = 0xffffu, kLongCell = 0xfffeu;
-    uint32_t* recw = reinterpret_cast<uint32_t*>(raw);
-    float* recf = reinterpret_cast<float*>(raw);
-    const int cn = (int)__builtin_amdgcn_readfirstlane((int)ccnt[c]);
-    // 1. the cell's record indices, one per lane: its four slots, then its chain (walked once; every lane reads the same word)
-    const uint2 sl4 = slots[c];
-    uint32_t idx = lane == 0 ? (sl4.x & 0xffffu) : lane == 1 ? (sl4.x >> 16) : lane == 2 ? (sl4.y & 0xffffu) : (sl4.y >> 16);
-    uint32_t cur = ohead[c];
-    for (int j = 4; j < cn; ++j) {
-        const uint32_t cs = (uint32_t)__builtin_amdgcn_readfirstlane((int)cur);
-        idx = lane == j ? cs : idx;
-        cur = cs != kEnd ? (uint32_t)link[cs] : kEnd;
-    }
-    const bool mine = lane < cn;
-    // 2. rank of every record = number of keys below its own (keys are source positions: all different)
-    const uint32_t key = mine ? recw[8 * idx + 7] : 0xffffffffu;
-    uint32_t rank = 0;
-    for (int t = 0; t < cn; ++t) rank += ((uint32_t)__builtin_amdgcn_readlane((int)key, t) < key) ? 1u : 0u;
-    // 3. lane r gets the index of the r-th record in raster order (forward permute among the cn active lanes)
-    uint32_t sorted = 0;
-    if (mine) sorted = (uint32_t)__builtin_amdgcn_ds_permute((int)(rank << 2), (int)idx);
-    // 4. lane (class k, channel ch) adds its sum over the records in that order
-    const int k = lane & 3, ch = lane >> 2;
-    const bool acc_on = ch < 1 + NCH;
-    const bool is_mask = NCH > NC && ch == 1 + NC;
-    const int doff = (ch >= 1 && ch <= NC) ? 3 + ch : 7;          // word of the record this lane multiplies the weight with
-    float acc = 0.0f;
-    for (int r = 0; r < cn; ++r) {
-        const uint32_t ir = (uint32_t)__builtin_amdgcn_readlane((int)sorted, r);
-        const float wv = recf[8 * ir + k];
-        const uint32_t dw = recw[8 * ir + doff];
-        const float dv = ch == 0 ? 1.0f : (is_mask ? (float)(dw & 1u) : __uint_as_float(dw));
-        acc += wv * dv;                                            // (density: the weight itself -- w * 1 is exact)
-    }
-    // 5. the class sums where the cell's readers expect them: one f4 (the four classes) per channel, in the first three records
-    const uint32_t ia = (uint32_t)__builtin_amdgcn_readlane((int)sorted, 0), ib = (uint32_t)__builtin_amdgcn_readlane((int)sorted, 1);
-    const uint32_t ic = (uint32_t)__builtin_amdgcn_readlane((int)sorted, 2);
-    if (acc_on) {
-        const uint32_t f4i = ch < 2 ? 2 * ia + ch : ch < 4 ? 2 * ib + (ch - 2) : 2 * ic;
-        recf[4 * f4i + k] = acc;
-    }
-    if (lane == 0) slots[c] = make_uint2(kLongCell | (ia << 16), ib | (ic << 16));
 }
 
 // exchange with the neighbouring lane (lanes 2j <-> 2j + 1): the pair's partner owns the other half of a 4-pixel group
@@ -2919,10 +2696,6 @@ __device__ __forceinline__ void sp_data_done(const SP& s, SpRawData<NC>& r, f4 (
     mc4 = nz_bytes(ma) & nz_bytes(mb);
 }
 
-template <int NC, bool MCH, typename TF, typename TO, typename GP, typename SP>
-__device__ __forceinline__ void sp_tile_atomics(const GP& p, const SP& s, float* acc, const uint32_t* __restrict__ lst, int nlist,
-                                                const SpTile& t, int n, int r0 = 0, int r1 = kSpTH);
-
 // The gather kernel reads its ~400 bytes of parameters from the KERNARG SEGMENT through a pointer that is made opaque at
 // every phase boundary (OFL_OPAQUE_S): the compiler then fetches what a phase needs with scalar loads where it needs it.
 // Left to itself it loads all ~100 dwords at the top, cannot keep them in the 102 SGPRs, spills them to VGPR lanes and
@@ -2932,418 +2705,6 @@ typedef const GatherParams __attribute__((address_space(4))) GatherParamsK;
 
 typedef const SplatParams __attribute__((address_space(4))) SplatParamsK;
 typedef const SplatParamsLean __attribute__((address_space(4))) SplatParamsLeanK;
-template <int NC, bool MCH, typename TF = float, typename TO = float, bool LEAN = false>
-__global__ __launch_bounds__(kSpNT2, OFL_SP_MINB) void splat_gather_kernel(const GatherParams p_by_value_unused) {
-    GatherParamsK* pp = (GatherParamsK*)__builtin_amdgcn_kernarg_segment_ptr();
-#define p (*pp)
-    constexpr int NCH = NC + (MCH ? 1 : 0);
-    constexpr uint32_t kEnd = 0xffffu, kLongCell = 0xfffeu;     // (kLongCell in a cell's first slot: phase S summed it)
-    // A CELL is a unit square of the destination grid: the records whose end point has floor(x, y) = (cx, cy).  The four
-    // corner classes of a destination pixel (X, Y) are the cells (X - kx, Y - ky), so one list per cell serves them all:
-    // (kSpTW + 1) x (kSpTH + 1) cells per tile, the first column / row being the cells left of / above the tile.
-    constexpr int kCW = kSpTW + 1, kCH = kSpTH + 1, kCells = kCW * kCH, kCellsP = (kCells + 63) / 64 * 64;
-    constexpr int kCellRounds = (kCellsP + kSpNT2 - 1) / kSpNT2;
-    // LDS: records (32 bytes each) | records per cell | the first 4 records of every cell, 16 bits each | head of the chain
-    // of a cell's 5th, 6th ... record (later: of its sorted list) | chain links
-    __shared__ __attribute__((aligned(16))) unsigned char raw[kSpQ * 32 + kCellsP * 4 + kCellsP * 8 + kCellsP * 4 + kSpQ * 2];
-    __shared__ int qcount;
-    // cells with more than two records (at most kSpQ / 3 of them), collected so that phase S works on them lane by lane
-    constexpr int kLongQ = (kSpQ / 3 + 7) & ~7;
-    __shared__ uint16_t lq[kLongQ];
-    __shared__ int lqn;
-    // ... and, of those, the cells with more than kSpLaneMax records: a WAVE orders and sums each of them (below)
-    // cells of five to kNet records: a sorting network in one lane's registers; longer ones: a wave (3 data channels: six, the
-    // eight-input network spills there and costs smooth flows 2 %; 2 channels: eight -- profiles/r4_splat_variants.txt section 8)
-    constexpr int kNet = OFL_SP_NET8 == 0 ? 0 : (OFL_SP_NET8 == 1 ? (NC == 3 ? 6 : 8) : OFL_SP_NET8), kLaneMax = kNet ? kNet : kSpLaneMax;
-    constexpr int kBigQ = kSpQ / (kLaneMax + 1) + 1;              // (every queued cell holds more than kLaneMax of the kSpQ records)
-    __shared__ uint16_t bq[kBigQ];
-    __shared__ int bqn;
-    f4* rec4 = reinterpret_cast<f4*>(raw);                            // rec4[2 * i] weights, rec4[2 * i + 1] data | key
-    const uint32_t* rwords = reinterpret_cast<const uint32_t*>(raw);  // key of record i: rwords[8 * i + 7]
-    uint32_t* ccnt = reinterpret_cast<uint32_t*>(raw + kSpQ * 32);    // [kCellsP]: records of the cell
-    uint2* slots = reinterpret_cast<uint2*>(ccnt + kCellsP);          // [kCellsP]: records 0 .. 3 of the cell (kEnd: none), raster order after phase S
-    uint32_t* ohead = reinterpret_cast<uint32_t*>(slots + kCellsP);   // [kCellsP]: chain of the records beyond four / sorted list of a long cell
-    uint16_t* link = reinterpret_cast<uint16_t*>(ohead + kCellsP);    // [kSpQ]: next record of the chain
-#define s (*reinterpret_cast<typename std::conditional<LEAN, SplatParamsLeanK, SplatParamsK>::type*>(&pp->s))   /* (see SplatParamsLean) */
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = s.w, h = s.h;
-    const uint32_t hw = (uint32_t)(h * w);
-    constexpr int kHalf = kSpNT2 / kSubLanes, kStep = 2 * kHalf;      // subtiles per half step (kSubLanes lanes each) / per step
-    int tx, ty, n;
-    if (!decode3(p.total, p.per_xcd, p.tiles_img, p.mi_m, p.mi_s, p.mx_m, p.mx_s, p.tiles_x, tx, ty, n)) return;
-    if (p.img_over[n] != 0) return;                                   // this image takes the global-atomics path instead
-    const uint32_t tile = (uint32_t)(n * (int)p.tiles_img + ty * p.tiles_x + tx);
-    const uint32_t* __restrict__ lst = p.list + (int64_t)tile * kBinCap;
-    // the first 32 entries of the list are fetched WITH its length (the list has a fixed address and kBinCap slots: entries
-    // past the length are stale ids that are never used): one round trip for the list, one for the end points, one for the data
-    const uint32_t pre[2] = {lst[tid / kSubLanes], lst[kHalf + tid / kSubLanes]};
-    const int nlist = min(p.cnt[tile], kBinCap);
-    OFL_OPAQUE_S(pp);
-    SpTile t;
-    sp_tile_setup<TF>(s, tx, ty, n, t);
-    const int dx0 = t.dx0, dy0 = t.dy0, ly = t.ly, lx2 = t.lx2;
-    int dflags = 0;
-    const int sl = tid & (kSubLanes - 1), srow = sl >> 2, sc4 = sl & 3;
-    // ---- A: walk the tile's list, 32 subtiles per step (4 source pixels per lane and half step), in three waves of loads:
-    // list -> flow + weight mask of both halves -> data of the 4-pixel groups that have a pixel in the tile.  The pixels
-    // whose cell lies in the tile (cell rows r0 .. r1) become LDS records and join their cell; qcount ends up as the number
-    // of records wanted (more than kSpQ: not all were kept).
-    // one half step: the hit test of a lane's 4 source pixels, ranks by ballot + popcount, records and cells in LDS
-    // (batching the LDS traffic of both half steps -- all rank atomics, then all record stores, then all slot stores -- was
-    // measured 6 % SLOWER: the longer live ranges cost more than the round trips saved)
-    auto process = [&](const SpSrc& q, int sx4, int sy, const f4 (&dat)[NC], uint32_t mc4, int r0, int r1) {
-        int cell[4];
-        unsigned long long m[4];
-        int wtot = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int cx = (int)__builtin_amdgcn_fmed3f(floorf(q.x[k]), -2.0f, (float)w) - dx0 + 1;
-            const int cy = (int)__builtin_amdgcn_fmed3f(floorf(q.y[k]), -2.0f, (float)h) - dy0 + 1;
-            const bool hit = ((q.on >> k) & 1u) != 0u && (uint32_t)cx < (uint32_t)kCW && cy >= r0 && cy <= r1;
-            cell[k] = hit ? cy * kCW + cx : -1;
-            m[k] = __ballot(hit);
-            wtot += __popcll(m[k]);
-        }
-        if (wtot != 0) {                                   // wave-uniform
-            int wbase = 0;
-            if (lane == 0) wbase = atomicAdd(&qcount, wtot);
-            wbase = __builtin_amdgcn_readfirstlane(wbase);
-            const unsigned long long below = (1ull << lane) - 1ull;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int pos = wbase + __popcll(m[k] & below);
-                wbase += __popcll(m[k]);
-                if (cell[k] >= 0 && pos < kSpQ) {
-                    const float xv = q.x[k], yv = q.y[k];
-                    const float x0 = floorf(xv), y0 = floorf(yv);
-                    const float wx0 = (x0 + 1.0f) - xv, wx1 = xv - x0, wy0 = (y0 + 1.0f) - yv, wy1 = yv - y0;   // utils.py:1110-1111
-                    rec4[2 * pos] = (f4){wy0 * wx0, wy0 * wx1, wy1 * wx0, wy1 * wx1};                        // utils.py:1114
-                    // key: raster position of the source pixel (15 bits each, checked by ofl_splat_tiled_f32) with the
-                    // mask-channel bit below it -- two records never share a position, so ordering by the whole word is raster order
-                    f4 dv = {0.f, 0.f, 0.f, __uint_as_float(((((uint32_t)sy << 15) | (uint32_t)(sx4 + k)) << 1) | ((mc4 >> (8 * k)) & 1u))};
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) dv[c] = s.data_sign * dat[c][k];
-                    rec4[2 * pos + 1] = dv;
-                    // the cell's first four records go to its slots (arrival order), later ones on a chain
-                    const uint32_t slot = atomicAdd(&ccnt[cell[k]], 1u);
-                    if (slot < 4u) reinterpret_cast<uint16_t*>(slots)[4 * cell[k] + (int)slot] = (uint16_t)pos;
-                    else link[pos] = (uint16_t)atomicExch(&ohead[cell[k]], (uint32_t)pos);
-                    // the cell's THIRD record makes it a cell phase S must order: exactly one thread sees slot 2, and it
-                    // queues the cell there and then -- no pass over the cell counters and no barrier for it afterwards
-                    // (round 4: -1.2 ... -3.3 %, profiles/r4_splat_variants.txt)
-                    if (slot == 2u) lq[atomicAdd(&lqn, 1)] = (uint16_t)cell[k];
-                }
-            }
-        }
-    };
-    // ---- A: walk the tile's list from entry `first`, 32 subtiles per step (4 source pixels per lane and half step): list ->
-    // flow, weight mask AND data of both halves in one wave of loads (fetching the data only for the 4-pixel groups that turn
-    // out to have a pixel in the tile saves a third of the bytes but costs a third dependent round trip: +10 % time -- a
-    // tile's life is a chain of round trips, not a bandwidth problem).  The pixels whose cell lies in the tile (cell rows
-    // r0 .. r1) become LDS records and join their cell; qcount ends up as the number of records wanted (more than kSpQ:
-    // not all were kept).
-    auto scan = [&](int r0, int r1, int first) {
-        OFL_OPAQUE_S(pp);
-        for (int base = first; base < nlist; base += kStep) {
-            SpSrc q[2];
-            int sx4[2], sy[2];
-            bool inb[2];
-            const bool two = base + kHalf < nlist;             // block-uniform: the second half step has entries
-#if OFL_SP_ISSUE_FIRST
-            // per half step: EVERY load first -- flow / positions, weight mask, data, mask-channel operands -- and only then the
-            // end points: one round trip instead of two (see sp_issue_src).  (Both half steps' loads at once would be one
-            // round trip for the rare tile with more than 64 listed subtiles too, but 70 live registers more: scratch.)
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                if (u == 1 && !two) continue;
-                const int e = base + u * kHalf + tid / kSubLanes;
-                const bool have = e < nlist;
-                const uint32_t sub = base == 0 ? pre[u] : (have ? lst[e] : 0u);
-                const uint32_t suby = fastdiv(sub, p.sx_m, p.sx_s), subx = sub - suby * (uint32_t)p.subs_x;
-                sx4[u] = (int)subx * kSubW + sc4 * 4; sy[u] = (int)suby * kSubH + srow;
-                inb[u] = have && (sx4[u] < w) && (sy[u] < h);
-                SpRaw raw_src;
-                SpRawData<NC> raw_dat;
-                sp_issue_src<TF>(s, n, sx4[u], sy[u], inb[u], (uint32_t)(sy[u] * w + sx4[u]), hw, raw_src);
-                if (inb[u]) sp_issue_data<NC, MCH, TF>(s, n, sx4[u], sy[u], hw, raw_dat);
-                f4 dat[NC];
-                uint32_t mc4 = 0x01010101u;
-#pragma unroll
-                for (int c = 0; c < NC; ++c) dat[c] = (f4){0.f, 0.f, 0.f, 0.f};
-                sp_src_done(s, sx4[u], sy[u], inb[u], raw_src, q[u]);
-                if (inb[u]) sp_data_done<NC>(s, raw_dat, dat, mc4);
-                process(q[u], sx4[u], sy[u], dat, mc4, r0, r1);
-            }
-#else
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                if (u == 1 && !two) { inb[1] = false; sx4[1] = sy[1] = 0; continue; }
-                const int e = base + u * kHalf + tid / kSubLanes;
-                const bool have = e < nlist;
-                const uint32_t sub = base == 0 ? pre[u] : (have ? lst[e] : 0u);
-                const uint32_t suby = fastdiv(sub, p.sx_m, p.sx_s), subx = sub - suby * (uint32_t)p.subs_x;
-                sx4[u] = (int)subx * kSubW + sc4 * 4; sy[u] = (int)suby * kSubH + srow;
-                const bool in = have && (sx4[u] < w) && (sy[u] < h);
-                sp_load_src<TF>(s, n, sx4[u], sy[u], in, (uint32_t)(sy[u] * w + sx4[u]), hw, q[u]);
-                inb[u] = in;
-            }
-            f4 dat[2][NC];
-            uint32_t mc4[2] = {0x01010101u, 0x01010101u};
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-#pragma unroll
-                for (int c = 0; c < NC; ++c) dat[u][c] = (f4){0.f, 0.f, 0.f, 0.f};
-                if (inb[u]) sp_load_data<NC, MCH, TF>(s, n, sx4[u], sy[u], hw, dat[u], mc4[u]);
-            }
-            process(q[0], sx4[0], sy[0], dat[0], mc4[0], r0, r1);
-            if (two) process(q[1], sx4[1], sy[1], dat[1], mc4[1], r0, r1);
-#endif
-        }
-    };
-    using std::integral_constant;
-    // bands of destination rows: 1 when every record fits the LDS; decided from the number of records the whole tile wants
-    int nb = 1;
-    bool over = false;
-    for (int attempt = 0; attempt < 2 && !over; ++attempt) {
-        const int rows = kSpTH / nb;
-        bool redo = false;
-        for (int band = 0; band < nb; ++band) {
-            const int r0 = band * rows, r1 = r0 + rows;
-#pragma unroll
-            for (int i = 0; i < kCellRounds; ++i)
-                if (tid + i * kSpNT2 < kCellsP) {
-                    ccnt[tid + i * kSpNT2] = 0u; ohead[tid + i * kSpNT2] = kEnd;
-                    slots[tid + i * kSpNT2] = make_uint2(0xffffffffu, 0xffffffffu);
-                }
-            if (tid == 0) {
-                qcount = 0;
-                lqn = 0;
-                bqn = 0;
-            }
-            __syncthreads();
-            scan(r0, r1, 0);
-            __syncthreads();                                   // records, cells and the count are in place
-            const int nrec = qcount;
-            if (nrec > kSpQ) {                                 // block-uniform
-                if (nb == 1) {                                 // a band of r rows sees about (r + 1) / 16 of the records
-                    nb = 2;
-                    if (nrec * (kSpTH / 2 + 1) > (kSpQ - kSpQ / 8) * kSpTH) nb = 4;
-                    if (nrec * (kSpTH / 4 + 1) > (kSpQ - kSpQ / 8) * kSpTH) over = true;   // a fold: straight to the float atomics
-                    redo = !over;
-                } else {
-                    over = true;
-                }
-                break;
-            }
-            // ---- S: every cell's records in raster order of their source pixels (ascending key) -- the order in which the
-            // reference's scatter_add_ adds them within a corner class.  One or two records need nothing (a + b = b + a, and
-            // the sums start from +0); three or four are sorted by a network in registers; a longer list (a compression or
-            // fold of the flow) becomes a chain sorted by insertion, walked by its readers.
-            bool toolong = false;
-            // Cells with one or two records need nothing (a + b = b + a, sums start from +0).  The others -- a few per cent of
-            // the cells, scattered over the lanes -- are first COLLECTED, then handled one per lane: put in raster order (four:
-            // a network in registers; more: insertion sort of the chain) and summed there and then, per corner class, in that
-            // order; the four class sums of every channel overwrite the cell's first three records and its readers add them
-            // as if they were one record.  (Every reader sorting and walking such cells itself kept 60 lanes of a wave idle
-            // while 4 of them worked: -20 % VALU instructions on the bench flow.)
-            const int nlong = lqn;                             // (queued by the scan; the barrier after it covers the queue)
-            for (int qi = tid; qi < nlong; qi += kSpNT2) {
-                const int c = lq[qi];
-                const uint32_t cn = ccnt[c];
-                if (cn > (uint32_t)kSpLong) { toolong = true; continue; }   // the limit is on the LENGTH: the same in every run
-                if (cn > (uint32_t)kLaneMax) { bq[atomicAdd(&bqn, 1)] = (uint16_t)c; continue; }   // a wave's job (below)
-                const uint2 sl4 = slots[c];
-                uint32_t e[4] = {sl4.x & 0xffffu, sl4.x >> 16, sl4.y & 0xffffu, sl4.y >> 16};
-                // the class sums, in raster order: product rounded, then added (as sp_use does for the short cells)
-                f4 sum[1 + NCH];
-#pragma unroll
-                for (int ch = 0; ch < 1 + NCH; ++ch) sum[ch] = (f4){0.f, 0.f, 0.f, 0.f};
-                auto add = [&](const f4 wv, const f4 dv) {
-                    sum[0] += wv;
-#pragma unroll
-                    for (int ch = 0; ch < NC; ++ch) sum[1 + ch] += wv * dv[ch];
-                    if (NCH > NC) sum[1 + NC] += wv * (float)(__float_as_uint(dv[3]) & 1u);
-                };
-                uint32_t ia, ib, ic;
-                if (cn <= 4u) {
-                    // three or four records (the bulk: 2 % of the cells of the bench flow against 0.25 % longer ones): ordered by a
-                    // network on (key, index) in registers and fetched by index all at once -- two dependent LDS round trips (keys,
-                    // records) instead of the eight of a walk along freshly written links
-                    uint32_t key[4];
-#pragma unroll
-                    for (int j4 = 0; j4 < 4; ++j4) key[j4] = e[j4] != kEnd ? rwords[8 * e[j4] + 7] : 0xffffffffu;
-#define OFL_CSWAP(a_, b_) { const bool sw = key[a_] > key[b_]; const uint32_t tk = sw ? key[b_] : key[a_], te = sw ? e[b_] : e[a_]; \
-                            key[b_] = sw ? key[a_] : key[b_]; e[b_] = sw ? e[a_] : e[b_]; key[a_] = tk; e[a_] = te; }
-                    OFL_CSWAP(0, 1) OFL_CSWAP(2, 3) OFL_CSWAP(0, 2) OFL_CSWAP(1, 3) OFL_CSWAP(1, 2)
-#undef OFL_CSWAP
-                    const bool four = e[3] != kEnd;                        // (kEnd sorts last: e[3] for three records)
-                    const uint32_t e3 = four ? e[3] : e[2];
-                    const f4 w0 = rec4[2 * e[0]], d0 = rec4[2 * e[0] + 1], w1 = rec4[2 * e[1]], d1 = rec4[2 * e[1] + 1];
-                    const f4 w2 = rec4[2 * e[2]], d2 = rec4[2 * e[2] + 1], w3 = rec4[2 * e3], d3 = rec4[2 * e3 + 1];
-                    add(w0, d0); add(w1, d1); add(w2, d2);
-                    if (four) add(w3, d3);
-                    ia = e[0]; ib = e[1]; ic = e[2];
-                } else if (kNet != 0 && cn <= (uint32_t)kNet) {
-                    // five to eight records: the chain is walked ONCE (its links), the (key, index) pairs are ordered by a sorting
-                    // network in registers (19 comparators for eight, 12 for six) and the records fetched by index -- ~6 dependent
-                    // LDS round trips instead of the ~2 n^2 / 4 of the insertion sort below (n = 8: 32)
-                    constexpr int M = kNet ? kNet : 8;
-                    static_assert(M == 8 || M == 6, "sorting network size");
-                    uint32_t ix[M], ky[M];
-#pragma unroll
-                    for (int j4 = 0; j4 < 4; ++j4) ix[j4] = e[j4];
-                    uint32_t cur = ohead[c];
-#pragma unroll
-                    for (int j4 = 4; j4 < M; ++j4) {
-                        const bool on = (uint32_t)j4 < cn;
-                        ix[j4] = on ? cur : kEnd;
-                        if (on) cur = link[cur];
-                    }
-#pragma unroll
-                    for (int j4 = 0; j4 < M; ++j4) ky[j4] = ix[j4] != kEnd ? rwords[8 * ix[j4] + 7] : 0xffffffffu;
-#define OFL_CSWAP8(a_, b_) { const bool sw = ky[a_] > ky[b_]; const uint32_t tk = sw ? ky[b_] : ky[a_], te = sw ? ix[b_] : ix[a_]; \
-                             ky[b_] = sw ? ky[a_] : ky[b_]; ix[b_] = sw ? ix[a_] : ix[b_]; ky[a_] = tk; ix[a_] = te; }
-                    if (M == 8) {
-                        OFL_CSWAP8(0, 1) OFL_CSWAP8(2, 3) OFL_CSWAP8(4, 5) OFL_CSWAP8(M - 2, M - 1)
-                        OFL_CSWAP8(0, 2) OFL_CSWAP8(1, 3) OFL_CSWAP8(4, M - 2) OFL_CSWAP8(5, M - 1)
-                        OFL_CSWAP8(1, 2) OFL_CSWAP8(5, M - 2) OFL_CSWAP8(0, 4) OFL_CSWAP8(3, M - 1)
-                        OFL_CSWAP8(1, 5) OFL_CSWAP8(2, M - 2)
-                        OFL_CSWAP8(1, 4) OFL_CSWAP8(3, M - 2)
-                        OFL_CSWAP8(2, 4) OFL_CSWAP8(3, 5)
-                        OFL_CSWAP8(3, 4)
-                    } else {
-                        OFL_CSWAP8(0, 1) OFL_CSWAP8(2, 3) OFL_CSWAP8(4, 5)
-                        OFL_CSWAP8(0, 2) OFL_CSWAP8(3, 5) OFL_CSWAP8(1, 4)
-                        OFL_CSWAP8(0, 1) OFL_CSWAP8(2, 3) OFL_CSWAP8(4, 5)
-                        OFL_CSWAP8(1, 2) OFL_CSWAP8(3, 4)
-                        OFL_CSWAP8(2, 3)
-                    }
-#undef OFL_CSWAP8
-                    // (unused slots carry the largest key: they sort last; five records at least are real)
-#pragma unroll
-                    for (int r = 0; r < M; ++r) {
-                        if (r < 5 || (uint32_t)r < cn) add(rec4[2 * ix[r]], rec4[2 * ix[r] + 1]);
-                        if (r == 3) asm volatile("" ::: "memory");     // (two batches of loads)
-                    }
-                    ia = ix[0]; ib = ix[1]; ic = ix[2];
-                } else {
-                    uint32_t cur = ohead[c];
-#pragma unroll
-                    for (int j4 = 0; j4 < 4; ++j4) { link[e[j4]] = (uint16_t)cur; cur = e[j4]; }
-                    uint32_t sorted = kEnd;
-                    while (cur != kEnd) {
-                        const uint32_t nxt = link[cur], k = rwords[8 * cur + 7];
-                        if (sorted == kEnd || rwords[8 * sorted + 7] > k) {
-                            link[cur] = (uint16_t)sorted; sorted = cur;
-                        } else {
-                            uint32_t q = sorted, qn = link[q];
-                            while (qn != kEnd && rwords[8 * qn + 7] < k) { q = qn; qn = link[q]; }
-                            link[cur] = (uint16_t)qn; link[q] = (uint16_t)cur;
-                        }
-                        cur = nxt;
-                    }
-                    ia = sorted; ib = link[ia]; ic = link[ib];
-                    for (uint32_t i = sorted; i != kEnd; i = link[i]) add(rec4[2 * i], rec4[2 * i + 1]);
-                }
-#pragma unroll
-                for (int ch = 0; ch < 1 + NCH; ++ch) {
-                    if (ch < 2) rec4[2 * ia + ch] = sum[ch];
-                    else if (ch < 4) rec4[2 * ib + (ch - 2)] = sum[ch];
-                    else rec4[2 * ic] = sum[ch];
-                }
-                slots[c] = make_uint2(kLongCell | (ia << 16), ib | (ic << 16));
-            }
-            if (nlong != 0) {                                  // (block-uniform: a tile without such cells needs no barrier here)
-                over = __syncthreads_or((int)toolong) != 0;
-                const int nbig = bqn;
-                if (!over && nbig != 0) {
-                    // Cells with more than kSpLaneMax records (a compression of the flow): one lane ordering such a cell by
-                    // insertion walks a chain in LDS -- two dependent round trips per comparison, ~n^2 / 4 of them: 0.1 ms for 64
-                    // records, and the kernel waited for the block that had drawn it (profiles/r4_splat_variants.txt, 4).  A WAVE
-                    // does it instead, one lane per record: the chain is walked once, every lane counts the keys below its own
-                    // (its rank in raster order), a permute puts the record indices in that order, and lane (class, channel)
-                    // adds its corner-class sum over the records in that order -- product rounded, then added, exactly what the
-                    // single lane did.  ~120 cycles per record instead of ~64 per record SQUARED.
-                    for (int b = tid >> 6; b < nbig; b += kSpNT2 / 64) sp_order_big_cell<NC, NCH>(raw, ccnt, slots, ohead, link, bq[b], lane);
-                    __syncthreads();
-                }
-            }
-            if (over) break;
-            // ---- C: the sums of this thread's 2 destination pixels (if their row is in the band), finalize.
-            // The pair reads 3 x 2 cells; every record of a cell is fetched once and added to each corner-class sum it
-            // belongs to (sp_use).
-            const bool mine = t.inimg && ly >= r0 && ly < r1;
-            float tot[2][1 + NCH];
-#pragma unroll
-            for (int k = 0; k < 2; ++k)
-#pragma unroll
-                for (int c = 0; c < 1 + NCH; ++c) tot[k][c] = 0.0f;
-            if (mine) {
-                float a[2][2][1 + NCH];                                   // [pixel of the pair][x-corner]: the corner row in hand
-                auto clear = [&]() {
-#pragma unroll
-                    for (int k = 0; k < 2; ++k)
-#pragma unroll
-                        for (int kx = 0; kx < 2; ++kx)
-#pragma unroll
-                            for (int c = 0; c < 1 + NCH; ++c) a[k][kx][c] = 0.0f;
-                };
-                const int cm = max(lx2 + 1, 0);                            // cell column of pixel 1's x-corner 1 = of pixel 0's x-corner 0
-                auto cell = [&](auto dc_, auto ky_) {
-                    constexpr int DC = decltype(dc_)::value, KY = decltype(ky_)::value;
-                    const int c = (ly + 1 - KY) * kCW + max(cm + DC, 0);   // (solo: pixel 0's own cells do not exist; it is never stored)
-                    const uint2 sl2 = slots[c];
-                    const uint32_t e0 = sl2.x & 0xffffu, e1 = sl2.x >> 16, e2 = sl2.y & 0xffffu, e3 = sl2.y >> 16;
-                    if (e0 == kEnd) return;
-                    if (e0 != kLongCell) {
-                        sp_use<NC, NCH, DC, KY>(rec4, e0, a);
-                        if (e1 != kEnd) sp_use<NC, NCH, DC, KY>(rec4, e1, a);
-                    } else {                                               // phase S left the cell's class sums
-                        sp_use_presum<NCH, DC, KY>(rec4, e1, e2, e3, a);
-                    }
-                };
-                clear();                                                   // corner row 0: classes 0, 1
-                cell(integral_constant<int, -1>{}, integral_constant<int, 0>{});
-                cell(integral_constant<int, 0>{}, integral_constant<int, 0>{});
-                cell(integral_constant<int, 1>{}, integral_constant<int, 0>{});
-#pragma unroll
-                for (int k = 0; k < 2; ++k)
-#pragma unroll
-                    for (int c = 0; c < 1 + NCH; ++c) tot[k][c] = a[k][0][c] + a[k][1][c];
-                clear();                                                   // corner row 1: classes 2, 3
-                cell(integral_constant<int, -1>{}, integral_constant<int, 1>{});
-                cell(integral_constant<int, 0>{}, integral_constant<int, 1>{});
-                cell(integral_constant<int, 1>{}, integral_constant<int, 1>{});
-#pragma unroll
-                for (int k = 0; k < 2; ++k)
-#pragma unroll
-                    for (int c = 0; c < 1 + NCH; ++c) tot[k][c] = (tot[k][c] + a[k][0][c]) + a[k][1][c];   // ((c0 + c1) + c2) + c3
-            }
-            OFL_OPAQUE_S(pp);
-            sp_finalize<NC, MCH, TF, TO>(s, t, tot, mine, dflags);
-            if (nb > 1) __syncthreads();                      // the next band re-uses the LDS
-        }
-        if (!redo) break;
-        dflags = 0;                                           // (nothing was finalized before the first band overflowed)
-        __syncthreads();
-    }
-    if (over) {
-        // a fold (more records than four bands hold, or > 64 sources in one cell)
-        // redone at once by this block with LDS float atomics (the records are dead: their LDS is the accumulator); whatever
-        // the first bands stored is overwritten, and the tile's flag word comes from here
-        if (tid == 0) atomicAdd(&p.stats[1], 1);
-        OFL_OPAQUE_S(pp);
-        sp_tile_atomics<NC, MCH, TF, TO>(p, s, reinterpret_cast<float*>(raw), lst, nlist, t, n);
-        return;
-    }
-    if (NC == 2 && s.dst_flags) {                             // (every thread of the block gets here)
-        dflags = wave_or_flags(dflags);
-        block_flag_or(&s.dst_flags[n], dflags);              // one access per block on the image's word (see block_flag_or)
-    }
-#undef s
-#undef p
-}
-
 // A tile the gather kernel cannot sum in order (a heavy fold of the flow): LDS float atomics over the tile's list (plane 0
 // density, then the data channels; the mask channel accumulates the INVALID weight, so that an all-valid pixel is exactly 1
 // in any order).  Tolerance instead of bit-exactness for these tiles; masks stay exact.  `acc` = (1 + NCH) * 512 floats of
@@ -3351,7 +2712,7 @@ __global__ __launch_bounds__(kSpNT2, OFL_SP_MINB) void splat_gather_kernel(const
 // stored (round 6: the second launch folds a BAND of a tile, not the whole tile).
 template <int NC, bool MCH, typename TF, typename TO, typename GP, typename SP>
 __device__ __forceinline__ void sp_tile_atomics(const GP& p, const SP& s, float* acc, const uint32_t* __restrict__ lst, int nlist,
-                                                const SpTile& t, int n, int r0, int r1) {
+                                                const SpTile& t, int n, int r0 = 0, int r1 = kSpTH) {
     constexpr int kPx = kSpTW * kSpTH, NCH = NC + (MCH ? 1 : 0);
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = s.w, h = s.h;
@@ -3415,7 +2776,7 @@ __device__ __forceinline__ void sp_tile_atomics(const GP& p, const SP& s, float*
 }
 
 // ------------------------------------------------------------------------------------------------
-// forward splat, gather formulation ON A DIET (round 6): splat_gather_kernel's algorithm with THREE blocks = 24 waves per CU
+// forward splat, gather formulation ON A DIET (round 6): round 5's gather kernel on THREE blocks = 24 waves per CU
 // ------------------------------------------------------------------------------------------------
 // profiles/r5_splat_scan.txt: the round-5 kernel is latency-bound -- one block per CU instead of two costs x 1.6 -- and what kept
 // it at two blocks was 81 KB of LDS and 119-125 VGPRs per 512-thread block.  Same phases (A scan, S order, C sum), same arithmetic,
@@ -3513,7 +2874,8 @@ template <int NV> struct SpAcc {
 };
 
 // One record of the cell whose column is DC (-1, 0, +1) cells from the pair's middle cell and whose row serves corner row KY, added
-// to the sums of the destination pixels that read it (see sp_use): weight = wy[KY] * wx[kx], rounded, then product with the data
+// to the sums of the destination pixels that read it: pixel 0 of the pair as its x-corner 1 (DC = -1) or 0 (DC = 0), pixel 1 as its
+// x-corner 1 (DC = 0) or 0 (DC = +1).  Weight = wy[KY] * wx[kx], rounded, then product with the data
 // rounded, then added.  NV = NC (+ 1: the mask channel is summed -- a tile all of whose records are valid leaves it out: its sums
 // are the density's, the same additions of the same weights).
 template <int NC, int NV, int DC, int KY>
@@ -3551,7 +2913,7 @@ __device__ __forceinline__ void sp2_use_presum(const f4* recA, const uint16_t* l
     }
 }
 
-// A cell with more than kNet (and at most 64) records, ordered and summed by the 64 lanes of one wave (see sp_order_big_cell).
+// A cell with more than kNet (and at most 64) records, ordered and summed by the 64 lanes of one wave.
 template <int NC, int NCH>
 __device__ __attribute__((noinline)) void sp2_order_big_cell(f4* recA, uint32_t* recB, uint16_t* link, uint32_t* cellw, int c, int lane) {
     const uint32_t cw = cellw[c];
@@ -3825,7 +3187,10 @@ __global__ __launch_bounds__(kSpNT2, REDO ? 4 : OFL_SP_MINB2) void splat_gather2
             }
         }
     };
-    // ---- A: walk the tile's list (see splat_gather_kernel): per half step EVERY load first, then the end points
+    // ---- A: walk the tile's list, 32 subtiles per half step (4 source pixels per lane): list -> flow, weight mask AND data of both
+    // halves in one wave of loads (the data of only the groups that turn out to hit the tile: a third fewer bytes, a third dependent
+    // round trip, +10 % time).  The pixels whose cell lies in the tile become LDS records and join their cell.
+    // Per half step EVERY load first, then the end points
     auto scan = [&](int r0, int r1, bool first) {
         const int sl = tid & (kSubLanes - 1), srow = sl >> 2, sc4 = sl & 3;
         OFL_OPAQUE_S(pp);
@@ -4340,7 +3705,7 @@ inline void magic_u32(uint32_t d, uint32_t& m, uint32_t& s) {   // d >= 1; see f
 
 // the promises of WarpParamsLean hold for this launch
 inline bool warp_is_lean(const WarpParams& p) {
-    return OFL_WARP_LEAN && (p.w & 3) == 0 && p.round_mode == OFL_ROUND_NONE && p.flow_flags == nullptr && p.shear != 0;
+    return (p.w & 3) == 0 && p.round_mode == OFL_ROUND_NONE && p.flow_flags == nullptr && p.shear != 0;
 }
 
 inline unsigned warp_geometry(WarpParams& p, int tile_w, int tile_h) {
@@ -4362,7 +3727,7 @@ inline unsigned warp_geometry(WarpParams& p, int tile_w, int tile_h) {
 // [2] VGPRs, [3] scratch bytes per thread) as the runtime reports them
 template <int NC, bool MCH, typename TF, typename TO>
 static int splat_launch_diet(const GatherParams* gp, unsigned grid, hipStream_t st, int extra_lds, int lean, int32_t* info) {
-    const bool ln = gp ? (NC >= 2 && OFL_SP_LEAN && splat_is_lean(gp->s)) : (NC >= 2 && lean != 0);
+    const bool ln = gp ? (NC >= 2 && splat_is_lean(gp->s)) : (NC >= 2 && lean != 0);
     const void* fn = ln ? (const void*)splat_gather2_kernel<NC, MCH, TF, TO, (NC >= 2)> : (const void*)splat_gather2_kernel<NC, MCH, TF, TO>;
     constexpr unsigned kRedoGrid = OFL_SP_REDOGRID;          // the second launch walks the redo list with this many blocks (2 per CU: 65 KB of LDS each)
     if (!gp) {
@@ -4429,7 +3794,7 @@ int ofl_wide_launch_column(const void* params, int nc, int valid, int add, int r
     constexpr int TT = kLdsT > 2 ? kLdsT : 3;
     const bool lean = warp_is_lean(q);
     constexpr int RT = OFL_ROWS_T;                                // tiles per column of the row-table kernel
-    if (OFL_WARP_ROWS && rows && lean && nc == 2 && (add || q.src_b || q.dst_flags)) {      // the flow-level variants with per-row extents
+    if (rows && lean && nc == 2 && (add || q.src_b || q.dst_flags)) {      // the flow-level variants with per-row extents
         const unsigned gr = RT == TT ? g : warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH);
         const int am = !add ? 0 : (q.add_is_flow ? 1 : 2);
 #define OFL_ROWS_F(V, A, S, D) OFL_KLAUNCH((warp_bwd_rows_kernel<RT, 2, V, A, S, D>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, st, q)
@@ -4442,7 +3807,7 @@ int ofl_wide_launch_column(const void* params, int nc, int valid, int add, int r
 #undef OFL_ROWS_F
         return (int)hipGetLastError();
     }
-    if (OFL_WARP_ROWS && rows && lean && !add) {                  // per-row extents instead of one sheared rectangle (warp_bwd_rows_kernel)
+    if (rows && lean && !add) {                  // per-row extents instead of one sheared rectangle (warp_bwd_rows_kernel)
         const unsigned gr = RT == TT ? g : warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH);
 #define OFL_ROWS_CASE(NC)                                                                                                    \
         if (valid) OFL_KLAUNCH((warp_bwd_rows_kernel<RT, NC, true>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, st, q);   \
@@ -4455,20 +3820,7 @@ int ofl_wide_launch_column(const void* params, int nc, int valid, int add, int r
 #undef OFL_ROWS_CASE
         return (int)hipGetLastError();
     }
-#if OFL_WARP_COL_ADD >= 2
-    if (add && OFL_WARP_REUSE && q.add_is_flow) {
-        if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, true, true, false, false, float, float, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-        else OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, false, true, false, false, float, float, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-        return (int)hipGetLastError();
-    }
-    if (add) {                                     // (the fused composition: 2 channels)
-        if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, true, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-        else OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-        return (int)hipGetLastError();
-    }
-#else
     if (add) return (int)hipErrorInvalidValue;     // (callers route an addend here only when the row-table kernel above takes it)
-#endif
 #define OFL_WIDE_CASE(NC)                                                                                                                   \
     if (lean) {                                                                                                                              \
         if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, NC, true, false, false, false, float, float, false, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);   \
@@ -4491,7 +3843,7 @@ int ofl_wide_launch_rows_small(const void* params, int nc, int valid, int add, i
     WarpParams q = *static_cast<const WarpParams*>(params);
     q.lds_bytes = kLdsBytes;
     hipStream_t st = (hipStream_t)stream;
-    if (!OFL_WARP_ROWS || !warp_is_lean(q) || q.src_b || q.dst_flags || nc < 1 || nc > 3 || (add && !(nc == 2 && q.add_is_flow))) return (int)hipErrorInvalidValue;
+    if (!warp_is_lean(q) || q.src_b || q.dst_flags || nc < 1 || nc > 3 || (add && !(nc == 2 && q.add_is_flow))) return (int)hipErrorInvalidValue;
     const unsigned gs = warp_geometry(q, kLdsTWQ * 4, (tiles == 1 ? 1 : 2) * kLdsTH);
 #define OFL_ROWS_S(T_, NC, V, A) OFL_KLAUNCH((warp_bwd_rows_kernel<T_, NC, V, A>), dim3(gs), dim3(kLdsNT), kRowsLdsBytes, st, q)
 #define OFL_ROWS_ST(T_)                                                                                   \
@@ -4510,7 +3862,7 @@ int ofl_wide_launch_rows_h(const void* params, void* stream) {
     q.lds_bytes = kLdsBytes;
     constexpr int RT = OFL_ROWS_T;
     const unsigned gr = warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH);
-    if (!OFL_WARP_ROWS || !warp_is_lean(q) || !q.valid || q.addend || q.dst_flags) return OFL_E_UNSUPPORTED;     // (not this kernel's launch: the caller takes the column / pair kernel)
+    if (!warp_is_lean(q) || !q.valid || q.addend || q.dst_flags) return OFL_E_UNSUPPORTED;     // (not this kernel's launch: the caller takes the column / pair kernel)
     if (q.src_b) OFL_KLAUNCH((warp_bwd_rows_kernel<RT, 2, true, 0, true, false, _Float16>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q);
     else OFL_KLAUNCH((warp_bwd_rows_kernel<RT, 2, true, 0, false, false, _Float16>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q);
     return (int)hipGetLastError();
@@ -4522,7 +3874,7 @@ int ofl_wide_launch_rows_grad(const void* params, int nc, int tiles, void* strea
     constexpr int RT = OFL_ROWS_T;
     const int tt = tiles == 1 ? 1 : (tiles == 2 ? 2 : RT);
     const unsigned gr = warp_geometry(q, kLdsTWQ * 4, tt * kLdsTH);
-    if (!OFL_WARP_ROWS || !warp_is_lean(q) || q.valid || q.src_b || q.dst_flags) return OFL_E_UNSUPPORTED;
+    if (!warp_is_lean(q) || q.valid || q.src_b || q.dst_flags) return OFL_E_UNSUPPORTED;
 #define OFL_ROWS_G(T_, NC) OFL_KLAUNCH((warp_bwd_rows_kernel<T_, NC, false, 0, false, false, float, float, false, true>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q)
 #define OFL_ROWS_GT(T_) switch (nc) { case 1: OFL_ROWS_G(T_, 1); break; case 2: OFL_ROWS_G(T_, 2); break; default: OFL_ROWS_G(T_, 3); break; }
     if (tt == 1) { OFL_ROWS_GT(1) } else if (tt == 2) { OFL_ROWS_GT(2) } else { OFL_ROWS_GT(RT) }
@@ -4536,7 +3888,7 @@ int ofl_wide_launch_rows_u8(const void* params, int nc, int dst_is_u8, void* str
     q.lds_bytes = kLdsBytes;
     constexpr int RT = OFL_ROWS_T;
     const unsigned gr = warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH);
-    if (!OFL_WARP_ROWS || (q.w & 3) != 0 || q.flow_flags || q.addend || q.src_b || q.dst_flags || !(nc == 1 || nc == 3)) return OFL_E_UNSUPPORTED;
+    if ((q.w & 3) != 0 || q.flow_flags || q.addend || q.src_b || q.dst_flags || !(nc == 1 || nc == 3)) return OFL_E_UNSUPPORTED;
 #define OFL_ROWS_U8(NC, V, TD) OFL_KLAUNCH((warp_bwd_rows_kernel<RT, NC, V, 0, false, false, uint8_t, TD, true>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q)
     if (dst_is_u8) {
         if (nc == 1) { if (q.valid) OFL_ROWS_U8(1, true, uint8_t); else OFL_ROWS_U8(1, false, uint8_t); }
@@ -4551,29 +3903,8 @@ int ofl_wide_launch_rows_u8(const void* params, int nc, int dst_is_u8, void* str
 int ofl_wide_launch_chan(const void* params, int valid, int rows, void* stream) {
     WarpParams q = *static_cast<const WarpParams*>(params);
     q.lds_bytes = kLdsBytes;
-#if OFL_WARP_CHAN_SUBS > 1
-    {   // three tiles side by side per block, in lockstep (see the kernel): 768 threads, 3 x 52 KB of LDS, one block = 12 waves per CU
-        constexpr int S = OFL_WARP_CHAN_SUBS;
-        WarpParams q3 = q;
-        const unsigned g3 = warp_geometry(q3, kLdsTWQ * 4 * S, kLdsTH);
-        static bool attr_set = false;                             // (more than 64 KB of dynamic LDS must be asked for, once per kernel)
-        if (!attr_set) {
-            hipFuncSetAttribute((const void*)warp_bwd_lds_chan_kernel<true, true, S>, hipFuncAttributeMaxDynamicSharedMemorySize, S * kLdsBytes);
-            hipFuncSetAttribute((const void*)warp_bwd_lds_chan_kernel<false, true, S>, hipFuncAttributeMaxDynamicSharedMemorySize, S * kLdsBytes);
-            hipFuncSetAttribute((const void*)warp_bwd_lds_chan_kernel<true, false, S>, hipFuncAttributeMaxDynamicSharedMemorySize, S * kLdsBytes);
-            hipFuncSetAttribute((const void*)warp_bwd_lds_chan_kernel<false, false, S>, hipFuncAttributeMaxDynamicSharedMemorySize, S * kLdsBytes);
-            attr_set = true;
-        }
-        if (warp_is_lean(q3)) {
-            if (valid) OFL_KLAUNCH((warp_bwd_lds_chan_kernel<true, true, S>), dim3(g3), dim3(kLdsNT * S), S * kLdsBytes, (hipStream_t)stream, q3);
-            else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, true, S>), dim3(g3), dim3(kLdsNT * S), S * kLdsBytes, (hipStream_t)stream, q3);
-        } else if (valid) OFL_KLAUNCH((warp_bwd_lds_chan_kernel<true, false, S>), dim3(g3), dim3(kLdsNT * S), S * kLdsBytes, (hipStream_t)stream, q3);
-        else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, false, S>), dim3(g3), dim3(kLdsNT * S), S * kLdsBytes, (hipStream_t)stream, q3);
-        return (int)hipGetLastError();
-    }
-#endif
     const unsigned g1 = warp_geometry(q, kLdsTWQ * 4, kLdsTH);
-    if (OFL_WARP_ROWS && OFL_WARP_CHAN_SUBS == 1 && rows && warp_is_lean(q)) {
+    if (rows && warp_is_lean(q)) {
         if (valid) OFL_KLAUNCH((warp_bwd_lds_chan_kernel<true, true, 1, true>), dim3(g1), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q);
         else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, true, 1, true>), dim3(g1), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q);
         return (int)hipGetLastError();
@@ -4589,7 +3920,6 @@ int ofl_wide_launch_chan(const void* params, int valid, int rows, void* stream) 
 int g_warp_path = 0;   // ofl_set_option(OFL_OPT_WARP_PATH, .): 0 auto, 1 generic direct-gather kernel only, 2 (= auto), 3 / 4 staged with two tiles / one tile per block whatever the launch size (tests), 5 = auto but more than 3 channels as separate launches of 3 (tests: the channel-loop kernel against them), 6 = auto but the sheared rectangle instead of per-row extents (tests, A/B), 7 = auto but plain lean launches on four-tile row-table columns whatever the size (tests)
 int g_warp_shear = 1;   // ofl_set_option(OFL_OPT_WARP_SHEAR, .)
 int g_splat_pass_images = 0;   // ofl_set_option(OFL_OPT_SPLAT_PASS_IMAGES, .): 0 = automatic (one pass unless the fallback accumulator of a pass would pass 2^31 floats)
-int g_splat_path = 0;   // ofl_set_option(OFL_OPT_SPLAT_PATH, .): 0 = the diet gather kernel (round 6: 16-24-byte records, one-word cells, 3 blocks per CU), 1 = round 5's gather kernel (tests compare the two bit for bit; A/B)
 int g_splat_extra_lds = 0;   // ofl_set_option(OFL_OPT_SPLAT_EXTRA_LDS, .): bytes of dynamic LDS added to the diet kernel's launches (occupancy experiments: 28 672 -> two blocks per CU, 65 536 -> one)
 int g_splat_fallback_slots = 0;   // ofl_set_option(OFL_OPT_SPLAT_FALLBACK_SLOTS, .): 0 = automatic (1 GiB); tests use 1 to exercise the rounds
 
@@ -4602,7 +3932,7 @@ int launch_warp_lds(const WarpParams& p, unsigned grid, hipStream_t st) {
             const unsigned gc = warp_geometry(q, kLdsTWQ * 4, kLdsT * kLdsTH);
             constexpr int TT = kLdsT > 2 ? kLdsT : 3;
             if (gc >= 6912u) {
-                if (OFL_WARP_ROWS_FLOWOPS && warp_is_lean(q) && g_warp_path != 6) return ofl_wide_launch_column(&p, 2, 1, 0, 1, (void*)st);   // 64 x 16 tiles, per-row extents
+                if (warp_is_lean(q) && g_warp_path != 6) return ofl_wide_launch_column(&p, 2, 1, 0, 1, (void*)st);   // 64 x 16 tiles, per-row extents
                 if (warp_is_lean(q)) OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, true, false, false, NC == 2, float, float, false, false, true>), dim3(gc), dim3(kLdsNT), kLdsBytes, st, q);
                 else OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, true, false, false, NC == 2>), dim3(gc), dim3(kLdsNT), kLdsBytes, st, q);
                 return (int)hipGetLastError();
@@ -4612,7 +3942,7 @@ int launch_warp_lds(const WarpParams& p, unsigned grid, hipStream_t st) {
         return (int)hipGetLastError();
     }
     if (NC == 2 && p.dst_flags) {                          // (host: only with a valid mask)
-        if (OFL_WARP_ROWS_FLOWOPS && kLdsT > 2 && valid && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4) {   // large lean launches: the row-table kernel keeps the flag by-product
+        if (kLdsT > 2 && valid && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4) {   // large lean launches: the row-table kernel keeps the flag by-product
             WarpParams q = p;
             if (warp_is_lean(q) && warp_geometry(q, kLdsTWQ * 4, kLdsT * kLdsTH) >= 6912u) return ofl_wide_launch_column(&p, 2, 1, add ? 1 : 0, 1, (void*)st);
         }
@@ -4622,36 +3952,35 @@ int launch_warp_lds(const WarpParams& p, unsigned grid, hipStream_t st) {
     }
     // the fused composition (an addend): row tables where the launch is lean, else -- large launches only -- the four-tile column kernels
     // (REUSE / lean twins: no scratch since round 5); small and forced-path launches fall through to the pair / one-tile kernels
-    if (OFL_WARP_COL_ADD && kLdsT > 2 && add && NC == 2 && !p.flow_flags) {
+    if (kLdsT > 2 && add && NC == 2 && !p.flow_flags) {
         WarpParams q = p;
         const unsigned g = warp_geometry(q, kLdsTWQ * 4, kLdsT * kLdsTH);
-        if (OFL_WARP_COL_ADD >= 2) return ofl_wide_launch_column(&p, NC, valid ? 1 : 0, 1, 0, (void*)st);
-        // large launches of mode 3 proper: 64 x 16 tiles with per-row extents (warp_bwd_rows_kernel<.., ADD>)
-        if (OFL_WARP_ROWS_ADD && NC == 2 && (p.add_is_flow || OFL_WARP_ROWS_FLOWOPS) && warp_is_lean(q) && g >= (g_warp_path == 0 && p.add_is_flow && OFL_WARP_ROWS_SMALL ? OFL_ROWS_T4_MIN : 6912u) && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4)
+        // large launches of mode 3 proper and of another addend: 64 x 16 tiles with per-row extents (warp_bwd_rows_kernel<.., ADD>)
+        if (warp_is_lean(q) && g >= (g_warp_path == 0 && p.add_is_flow ? OFL_ROWS_T4_MIN : 6912u) && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4)
             return ofl_wide_launch_column(&p, NC, valid ? 1 : 0, 1, 1, (void*)st);
-        if (OFL_WARP_ROWS_SMALL && NC == 2 && p.add_is_flow && warp_is_lean(q) && g < OFL_ROWS_T4_MIN && g_warp_path == 0) {     // small mode 3
+        if (p.add_is_flow && warp_is_lean(q) && g < OFL_ROWS_T4_MIN && g_warp_path == 0) {     // small mode 3
             WarpParams q1 = p;
             return ofl_wide_launch_rows_small(&p, 2, valid ? 1 : 0, 1, warp_geometry(q1, kLdsTWQ * 4, kLdsTH) < OFL_ROWS_T1_MAX ? 1 : 2, (void*)st);
         }
         // the four-tile column kernels below are for LARGE launches on the automatic path (small launches keep the pair /
         // one-tile kernels further down -- half as many, twice as long blocks lose there -- and OFL_OPT_WARP_PATH 3 / 4 must reach them)
         if (g >= 6912u && g_warp_path != 3 && g_warp_path != 4) {
-        if (OFL_WARP_REUSE && NC == 2 && p.add_is_flow) {
-            if (warp_is_lean(q)) {
-                if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, true, true, false, false, float, float, false, true, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-                else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, false, true, false, false, float, float, false, true, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-            } else if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, true, true, false, false, float, float, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-            else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, false, true, false, false, float, float, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+            if (p.add_is_flow) {                       // (mode 3 proper: the flow registers are the addend, REUSE)
+                if (warp_is_lean(q)) {
+                    if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, true, true, false, false, float, float, false, true, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+                    else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, false, true, false, false, float, float, false, true, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+                } else if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, true, true, false, false, float, float, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+                else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, false, true, false, false, float, float, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+                return (int)hipGetLastError();
+            }
+            if (warp_is_lean(q)) {                     // (the addend is another flow: the outer `flow - (...)` of modes 1-2, Flow.combine's cells)
+                if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, true, true, false, false, float, float, false, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+                else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, false, true, false, false, float, float, false, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+                return (int)hipGetLastError();
+            }
+            if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, true, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+            else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
             return (int)hipGetLastError();
-        }
-        if (warp_is_lean(q)) {                     // (the addend is another flow: the outer `flow - (...)` of modes 1-2, Flow.combine's cells)
-            if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, true, true, false, false, float, float, false, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-            else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, false, true, false, false, float, float, false, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-            return (int)hipGetLastError();
-        }
-        if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, true, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-        else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-        return (int)hipGetLastError();
         }
     }
     // a plain warp (Flow.apply 't' of an image or a flow): columns of kLdsT tiles -- unless the launch is SMALL: a column block
@@ -4667,7 +3996,7 @@ int launch_warp_lds(const WarpParams& p, unsigned grid, hipStream_t st) {
         const unsigned g1 = warp_geometry(q1, kLdsTWQ * 4, kLdsTH);
         if (g_warp_path == 7 && !add && warp_is_lean(q1)) return ofl_wide_launch_column(&p, NC, valid ? 1 : 0, 0, 1, (void*)st);   // (tests / experiments: four-tile columns with row tables whatever the size)
         // small plain launches on the row-table kernel (1 tile per block for tiny ones, else 2): see ofl_wide_launch_rows_small
-        if (OFL_WARP_ROWS_SMALL && !add && !p.flow_flags && g_warp_path == 0 && warp_is_lean(q1)) {
+        if (!add && !p.flow_flags && g_warp_path == 0 && warp_is_lean(q1)) {
             WarpParams q4 = p;
             const unsigned g4 = warp_geometry(q4, kLdsTWQ * 4, kLdsT * kLdsTH);
             if (g4 < OFL_ROWS_T4_MIN) return ofl_wide_launch_rows_small(&p, NC, valid ? 1 : 0, 0, g1 < OFL_ROWS_T1_MAX ? 1 : 2, (void*)st);
@@ -4688,12 +4017,8 @@ int launch_warp_lds(const WarpParams& p, unsigned grid, hipStream_t st) {
     }
     WarpParams q = p;
     const unsigned g = (kLdsT > 2 && !add && !p.flow_flags) ? warp_geometry(q, kLdsTWQ * 4, kLdsT * kLdsTH) : 0u;
-    if (g >= kColumnMinGroups && g_warp_path != 3) {
-        if (OFL_WARP_WIDE) return ofl_wide_launch_column(&p, NC, valid ? 1 : 0, 0, g_warp_path != 6, (void*)st);    // 64 x 16 tiles: -1.9 % (see kLdsNT)
-        if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, true, false>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-        else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, false, false>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-        return (int)hipGetLastError();
-    }
+    if (g >= kColumnMinGroups && g_warp_path != 3)
+        return ofl_wide_launch_column(&p, NC, valid ? 1 : 0, 0, g_warp_path != 6, (void*)st);    // 64 x 16 tiles: -1.9 % (see kLdsNT)
 #define OFL_LAUNCH_L(V, A)                                                                                       \
     if (valid == V && add == A) {                                                                                \
         OFL_KLAUNCH((warp_bwd_lds_kernel<NC, V, A>), dim3(grid), dim3(kLdsNT), kLdsBytes, st, p);          \
@@ -4792,11 +4117,8 @@ inline unsigned fallback_resident_blocks(const void* kernel, int which) {
 
 template <int NC, bool MCH, typename TF = float, typename TO = float>
 int launch_splat_gather2(const GatherParams& gp, unsigned grid, hipStream_t st) {
-    // round 6: the diet kernel (3 blocks per CU) unless the tests / an A-B ask for round 5's (32-byte records, 2 blocks per CU)
-    if (g_splat_path != 1) return ofl_splat_launch_gather_diet(&gp, NC, MCH ? 1 : 0, std::is_same<TF, float>::value ? 0 : (std::is_same<TO, float>::value ? 1 : 2), grid, (void*)st, g_splat_extra_lds);
-    if (NC >= 2 && OFL_SP_LEAN && splat_is_lean(gp.s)) OFL_KLAUNCH((splat_gather_kernel<NC, MCH, TF, TO, (NC >= 2)>), dim3(grid), dim3(kSpNT2), 0, st, gp);
-    else OFL_KLAUNCH((splat_gather_kernel<NC, MCH, TF, TO>), dim3(grid), dim3(kSpNT2), 0, st, gp);
-    return (int)hipGetLastError();
+    // the diet kernel (3 blocks per CU), compiled in its own translation unit (ofl_splat_gather.hip)
+    return ofl_splat_launch_gather_diet(&gp, NC, MCH ? 1 : 0, std::is_same<TF, float>::value ? 0 : (std::is_same<TO, float>::value ? 1 : 2), grid, (void*)st, g_splat_extra_lds);
 }
 
 template <int NC>
@@ -4833,12 +4155,12 @@ int ofl_internal_warp_grad_flow_lds(const float* flow, int64_t flow_bs, float fl
     p.shear = (g_warp_shear && (int64_t)h + 4 * (int64_t)w + 8 < 32760) ? 1 : 0;
     const unsigned g = warp_geometry(p, kLdsTWQ * 4, kLdsT * kLdsTH);
     constexpr int TT = kLdsT > 2 ? kLdsT : 3;
-    if (OFL_WARP_ROWS_FLOWOPS && warp_is_lean(p) && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4) {   // 64 x 16 tiles, per-row extents
-        if (g >= (OFL_WARP_ROWS_SMALL && g_warp_path == 0 ? OFL_ROWS_T4_MIN : 6912u) || g_warp_path == 7) {
+    if (warp_is_lean(p) && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4) {   // 64 x 16 tiles, per-row extents
+        if (g >= (g_warp_path == 0 ? OFL_ROWS_T4_MIN : 6912u) || g_warp_path == 7) {
             const int rr = ofl_wide_launch_rows_grad(&p, c, OFL_ROWS_T, (void*)st);
             if (rr != OFL_E_UNSUPPORTED) return rr;
         }
-        if (OFL_WARP_ROWS_SMALL && g_warp_path == 0) {            // small launches (the shapes training runs at): one tile per block for tiny ones, else two
+        if (g_warp_path == 0) {            // small launches (the shapes training runs at): one tile per block for tiny ones, else two
             WarpParams q1 = p;
             const int rr = ofl_wide_launch_rows_grad(&p, c, warp_geometry(q1, kLdsTWQ * 4, kLdsTH) < OFL_ROWS_T1_MAX ? 1 : 2, (void*)st);
             if (rr != OFL_E_UNSUPPORTED) return rr;
@@ -4864,14 +4186,13 @@ __attribute__((visibility("default"))) const char* ofl_last_kernel_name(void) {
     return g_ofl_last_kernel ? hipKernelNameRefByPtr(g_ofl_last_kernel, nullptr) : "";
 }
 
-__attribute__((visibility("default"))) int ofl_version(void) { return 34; }   // 34: ofl_visualise_workspace_ints / ofl_visualise_range_f32 / ofl_visualise_u8 (ofl_visualise.hip); 33: the gather splat's diet kernel (ofl_splat_gather.hip), OFL_OPT_SPLAT_PATH / OFL_OPT_SPLAT_EXTRA_LDS, ofl_splat_gather_info; 32: OFL_OPT_WARP_PATH value 7 (four-tile row-table columns whatever the size); row tables for small launches, the other flow-level warps, fp16 / uint8 sources, the gradient-wrt-flow pass; 31: OFL_OPT_WARP_PATH value 6 (the sheared rectangle instead of per-row extents: warp_bwd_rows_kernel is the default for large lean launches); 30: OFL_OPT_WARP_PATH value 5 (more than 3 channels as launches of 3; the default is ONE launch that loops over the channels); 29: ofl_splat_tile_geometry (64 x 16 destination tiles); 28: ofl_resize_bilinear_f32; 27: ofl_warp_valid_f32 (ofl_aux_kernels.hip); 26: bounded fallback accumulator of the gather splat (ofl_splat_tiled_fallback_images); 25: ofl_flow_flags_host with sharded arrival counters and {serial, word} pairs, ofl_flow_from_matrix_f32; 24: ofl_flow_flags_host (+ ofl_host_words_alloc / _free); 23: scratch argument of ofl_splat_grad_f32; 22: ofl_splat_sum_f32; 21: ofl_flag_words_or_i32, splat workspace without the fold-tile list; 20: fp16-stored flows read directly (ofl_splat_tiled_f16, ofl_warp_bwd_h_f32, flags-only ofl_flow_from_f16); 19: gather-formulation splat (workspace layout), ofl_warp_bwd_win_f32 / ofl_splat_tiled_win_f32 (padded apply); 18: ofl_aux_kernels.hip (backward passes, point sampler, extents); 13: dst_flags in ofl_warp_bwd_f32 / ofl_splat_tiled_f32, fixed-address splat queues; 14: data_b; 15: src_b; 16: ofl_warp_bwd_u8; 17: ofl_flow_from_f16
+__attribute__((visibility("default"))) int ofl_version(void) { return 35; }   // 35: OFL_OPT_SPLAT_PATH retired; 34: ofl_visualise_workspace_ints / ofl_visualise_range_f32 / ofl_visualise_u8 (ofl_visualise.hip); 33: the gather splat's diet kernel (ofl_splat_gather.hip), OFL_OPT_SPLAT_PATH / OFL_OPT_SPLAT_EXTRA_LDS, ofl_splat_gather_info; 32: OFL_OPT_WARP_PATH value 7 (four-tile row-table columns whatever the size); row tables for small launches, the other flow-level warps, fp16 / uint8 sources, the gradient-wrt-flow pass; 31: OFL_OPT_WARP_PATH value 6 (the sheared rectangle instead of per-row extents: warp_bwd_rows_kernel is the default for large lean launches); 30: OFL_OPT_WARP_PATH value 5 (more than 3 channels as launches of 3; the default is ONE launch that loops over the channels); 29: ofl_splat_tile_geometry (64 x 16 destination tiles); 28: ofl_resize_bilinear_f32; 27: ofl_warp_valid_f32 (ofl_aux_kernels.hip); 26: bounded fallback accumulator of the gather splat (ofl_splat_tiled_fallback_images); 25: ofl_flow_flags_host with sharded arrival counters and {serial, word} pairs, ofl_flow_from_matrix_f32; 24: ofl_flow_flags_host (+ ofl_host_words_alloc / _free); 23: scratch argument of ofl_splat_grad_f32; 22: ofl_splat_sum_f32; 21: ofl_flag_words_or_i32, splat workspace without the fold-tile list; 20: fp16-stored flows read directly (ofl_splat_tiled_f16, ofl_warp_bwd_h_f32, flags-only ofl_flow_from_f16); 19: gather-formulation splat (workspace layout), ofl_warp_bwd_win_f32 / ofl_splat_tiled_win_f32 (padded apply); 18: ofl_aux_kernels.hip (backward passes, point sampler, extents); 13: dst_flags in ofl_warp_bwd_f32 / ofl_splat_tiled_f32, fixed-address splat queues; 14: data_b; 15: src_b; 16: ofl_warp_bwd_u8; 17: ofl_flow_from_f16
 
 __attribute__((visibility("default"))) int ofl_set_option(int32_t key, int32_t value) {
     if (key == OFL_OPT_WARP_PATH && value >= 0 && value <= 7) { g_warp_path = value; return OFL_OK; }
     if (key == OFL_OPT_WARP_SHEAR && (value == 0 || value == 1)) { g_warp_shear = value; return OFL_OK; }
     if (key == OFL_OPT_SPLAT_PASS_IMAGES && value >= 0) { g_splat_pass_images = value; return OFL_OK; }
     if (key == OFL_OPT_SPLAT_FALLBACK_SLOTS && value >= 0) { g_splat_fallback_slots = value; return OFL_OK; }
-    if (key == OFL_OPT_SPLAT_PATH && (value == 0 || value == 1)) { g_splat_path = value; return OFL_OK; }
     if (key == OFL_OPT_SPLAT_EXTRA_LDS && value >= 0 && value <= 100 * 1024) { g_splat_extra_lds = value; return OFL_OK; }
     return OFL_E_ARG;
 }
@@ -4928,13 +4249,13 @@ static int warp_bwd_impl(
         const unsigned g = warp_geometry(p, kLdsTWQ * 4, 2 * kLdsTH);
         // more than 3 channels of a plain warp: ONE launch that walks the channels inside the block (warp_bwd_lds_chan_kernel)
         // (with the valid area wanted the first group is 3 channels + the mask plane: below 7 channels two launches of 3 are as good or better)
-        if (OFL_WARP_CHAN && c >= (valid ? 7 : 4) && (w & 3) == 0 && !addend && !src_b && !dst_flags && g_warp_path != 5) {
+        if (c >= (valid ? 7 : 4) && (w & 3) == 0 && !addend && !src_b && !dst_flags && g_warp_path != 5) {
             WarpParams q = p;
             const unsigned g1 = warp_geometry(q, kLdsTWQ * 4, kLdsTH);
             // 64 x 16 tiles for large launches -- and, with per-row extents (lean, two channel groups or more), for EVERY size: B = 1 C = 64
             // 0.355 -> 0.255 ms, C = 16 0.071 -> 0.054 ms against the 32 x 16 rectangle version (tools/bench_chan.py --batch 1)
-            const bool rows_chan = OFL_WARP_ROWS && g_warp_path != 6 && c >= 7 && warp_is_lean(q);
-            if (OFL_WARP_CHAN_WIDE && (g1 >= OFL_WARP_CHAN_WIDE_MIN || rows_chan)) return ofl_wide_launch_chan(&p, p.valid ? 1 : 0, rows_chan ? 1 : 0, (void*)st);   // (row extents from two channel groups on: with one group their set-up is not amortised -- C = 4: 0.148 against 0.138 ms)
+            const bool rows_chan = g_warp_path != 6 && c >= 7 && warp_is_lean(q);
+            if (g1 >= OFL_WARP_CHAN_WIDE_MIN || rows_chan) return ofl_wide_launch_chan(&p, p.valid ? 1 : 0, rows_chan ? 1 : 0, (void*)st);   // (row extents from two channel groups on: with one group their set-up is not amortised -- C = 4: 0.148 against 0.138 ms)
             if (warp_is_lean(q)) {
                 if (q.valid) OFL_KLAUNCH((warp_bwd_lds_chan_kernel<true, true>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q);
                 else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, true>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q);
@@ -5028,7 +4349,7 @@ __attribute__((visibility("default"))) int ofl_warp_bwd_u8(
         q.src = reinterpret_cast<const float*>(src + c0 * hw);             // (the uint8 kernels re-read these as byte pointers)
         q.dst = dst_is_u8 ? reinterpret_cast<float*>(static_cast<uint8_t*>(dst) + c0 * hw) : static_cast<float*>(dst) + c0 * hw;
         if (c0 > 0) { q.valid = nullptr; q.src_mask = nullptr; }
-        if (OFL_WARP_ROWS_FLOWOPS && (nc == 1 || nc == 3) && (w & 3) == 0 && kLdsT > 2 && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4) {
+        if ((nc == 1 || nc == 3) && (w & 3) == 0 && kLdsT > 2 && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4) {
             WarpParams qg = q;                           // large launches: 64 x 16 tiles, per-row extents
             if (warp_geometry(qg, kLdsTWQ * 4, kLdsT * kLdsTH) >= 6912u) { rc = ofl_wide_launch_rows_u8(&q, nc, dst_is_u8, stream); if (rc == OFL_OK) continue; if (rc != OFL_E_UNSUPPORTED) return rc; }
         }
@@ -5083,7 +4404,7 @@ __attribute__((visibility("default"))) int ofl_warp_bwd_h_f32(
         constexpr int TT = kLdsT > 2 ? kLdsT : 3;
         if (gc >= 6912u) {
             const bool lean = warp_is_lean(q);
-            if (OFL_WARP_ROWS_FLOWOPS && lean && g_warp_path != 6) {                                                  // 64 x 16 tiles, per-row extents
+            if (lean && g_warp_path != 6) {                                                  // 64 x 16 tiles, per-row extents
                 const int rr = ofl_wide_launch_rows_h(&p, stream);
                 if (rr != OFL_E_UNSUPPORTED) return rr;                                                            // (a launch it declines falls through to the column kernel)
             }

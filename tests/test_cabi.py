@@ -100,6 +100,7 @@ def test_round3_entry_points_reject_bad_arguments_without_a_gpu():
     assert (tw.value, th.value) in ((32, 16), (64, 16)) and cap.value == 256 * (tw.value // 32)
     assert lib.ofl_splat_tile_geometry(None, None, None) == 0
     assert lib.ofl_set_option(5, -1) == -3 and lib.ofl_set_option(5, 0) == 0
+    assert lib.ofl_set_option(6, 0) == -3 and lib.ofl_set_option(6, 1) == -3      # (6: the retired gather-kernel choice, now an unknown key)
 
 
 def test_no_gpu_means_loud_failure(monkeypatch):

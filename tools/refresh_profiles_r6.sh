@@ -42,7 +42,7 @@ for sg in 2 8; do for pass in "fetch FETCH_SIZE" "write WRITE_SIZE TCC_HIT_sum T
 done; done
 { echo "$BOX"; for sg in 2 8; do echo "== B = 8, C = 64, sigma $sg: algorithmic bytes per launch = (8 + 8 * 64 + 1) x 8 x 1080 x 1920 = $((521 * 8 * 1080 * 1920))"; python3 tools/pmc_summary.py $O/chan_s$sg warp_bwd_lds_chan; done; } > $O/chan_pmc.txt 2>&1
 # the splat: timings per launch, occupancy sweep, PMC traffic and SQ counters (apply 's', B = 16)
-{ echo "$BOX"; tools/prof_splat_kernels.sh r6final/splat_k 2 8 12; python tools/splat_occupancy.py; python tools/ab_splat_kernels.py --rounds 5; } > $O/splat_kernels.txt 2>/dev/null
+{ echo "$BOX"; tools/prof_splat_kernels.sh r6final/splat_k 2 8 12; python tools/splat_occupancy.py; } > $O/splat_kernels.txt 2>/dev/null
 for pass in "fetch FETCH_SIZE" "write WRITE_SIZE" "sq SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR" "lds SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_ANY SQ_WAVES SQ_WAIT_INST_ANY"; do
   set -- $pass; name=$1; shift
   (cd /tmp && timeout 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/splat_$name -- python3 $R/tools/bench_ops.py --only apply_s --batch 16 --iters 5 > $O/splat_$name.log 2>&1)

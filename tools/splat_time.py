@@ -13,13 +13,11 @@ ap.add_argument("--sigma", type=float, nargs="+", default=[2.0, 8.0, 12.0])
 ap.add_argument("--batch", type=int, default=16)
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--iters", type=int, default=10)
-ap.add_argument("--kernel", type=int, default=0)
 a = ap.parse_args()
 dev = torch.device('cuda', 0)
 n, h, w = a.batch, 1080, 1920
 _native.collect_splat_stats = True
-_native.set_splat_gather_kernel(a.kernel)
-tag = os.path.basename(os.environ.get("OFL_HIP_LIB", "default")) + ("" if a.kernel == 0 else " (round-5 kernel)")
+tag = os.path.basename(os.environ.get("OFL_HIP_LIB", "default"))
 out = []
 for sigma in a.sigma:
     f1 = bench.smooth_flow(n, h, w, sigma, 1000, dev)
