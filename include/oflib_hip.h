@@ -538,6 +538,31 @@ int ofl_visualise_u8(const void* flow, int64_t flow_bs, int32_t flow_half, const
                      int32_t show_mask_borders, const double* range_max, int32_t mode, int32_t layout, uint8_t* out, int32_t n,
                      int32_t h, int32_t w, void* stream);
 
+/*
+ * Flow.matrix (flow_class.py:1566-1646) and get_flow_matrix (flow_operations.py:306-336): the similarity (dof 4), affine map
+ * (dof 6) or homography (dof 8) of the point pairs of a flow field.  ofl_matrix.hip; the numerics are DEFINED in DESIGN.md 3.10
+ * (the reference calls OpenCV's estimators; restated, not checked against OpenCV; no Levenberg-Marquardt polish).
+ *
+ * ofl_matrix_workspace_bytes(n, h, w, dof, method): bytes of the workspace ofl_matrix_fit_f64 needs (8-byte aligned; cleared
+ *   inside the call by one hipMemsetAsync on `stream`), or OFL_E_SHAPE / OFL_E_ARG.
+ *
+ * ofl_matrix_fit_f64 <- the loop of flow_class.py:1632-1646: per image, the point pairs of :1600-1610 in float64 (ref 0 = 't':
+ *   dst = grid, src = grid - vecs; 1 = 's': src = grid, dst = grid + vecs), of the pixels where mask != 0 (mask NULL = all; the
+ *   `masked` argument), fitted by method 0 = 'lms' (float64 least squares: closed form / 3 x 3 normal equations / normalised DLT
+ *   with cyclic Jacobi), 1 = 'ransac' (256 hypotheses, inliers within 3 px, most inliers wins) or 2 = 'lmeds' (128 hypotheses,
+ *   smallest exact median of the squared residuals wins), the robust methods followed by ONE least-squares fit of the winner's
+ *   inliers.  dof 4 / 6 / 8; any method with any dof (the 'lms' -> 'ransac' switch of :1612-1615 is the caller's).
+ *   flow [N,2,H,W] fp32 (flow_half = 0) or fp16 (1), batch stride flow_bs (elements); mask [N,H,W] bytes, stride mask_bs.
+ *   out_matrix float64[N * 9] (row-major 3 x 3; zeros where status != 0), out_info int32[N * 4] = {n_valid, the winner's k (-1 for
+ *   'lms'), inlier count, status}; status 0 ok, 1 fewer valid pixels than the model needs (2 / 3 / 4), 2 no non-degenerate
+ *   hypothesis, 3 singular fit of the inliers.  Integer atomics only and fixed summation order: bitwise reproducible, and image
+ *   i's result does not depend on the batch.  h * w < 2^31, n <= 65535.
+ */
+int64_t ofl_matrix_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t dof, int32_t method);
+int ofl_matrix_fit_f64(const void* flow, int64_t flow_bs, int32_t flow_half, int32_t ref, const uint8_t* mask, int64_t mask_bs,
+                       int32_t n, int32_t h, int32_t w, int32_t dof, int32_t method, void* workspace, double* out_matrix,
+                       int32_t* out_info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

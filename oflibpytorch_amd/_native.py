@@ -18,7 +18,7 @@ import torch
 from . import _build
 
 FLAG_NONFINITE, FLAG_NZ, FLAG_NZ_THR, FLAG_NZ_MASKED, FLAG_NZ_THR_MASKED = 1, 2, 4, 8, 16
-ABI_VERSION = 35              # ofl_version() of the library this file's argtypes describe
+ABI_VERSION = 36              # ofl_version() of the library this file's argtypes describe
 ROUND_NONE, ROUND_RINT, ROUND_U8 = 0, 1, 2
 THRESHOLD = 1e-3
 
@@ -27,7 +27,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_warp_bwd_grad_f32", "ofl_splat_grad_f32", "ofl_sample_pts_f32", "ofl_sample_pts_grad_f32",
             "ofl_flow_extents_f32", "ofl_flag_words_or_i32", "ofl_splat_sum_f32", "ofl_warp_bwd_win_f32", "ofl_splat_tiled_win_f32", "ofl_splat_tiled_f16",
             "ofl_warp_bwd_h_f32", "ofl_flow_flags_host", "ofl_host_words_alloc", "ofl_host_words_free", "ofl_flow_from_matrix_f32", "ofl_splat_tiled_fallback_images", "ofl_warp_valid_f32", "ofl_resize_bilinear_f32", "ofl_splat_tile_geometry", "ofl_splat_gather_info", "ofl_last_kernel_name",
-            "ofl_visualise_workspace_ints", "ofl_visualise_range_f32", "ofl_visualise_u8")
+            "ofl_visualise_workspace_ints", "ofl_visualise_range_f32", "ofl_visualise_u8",
+            "ofl_matrix_workspace_bytes", "ofl_matrix_fit_f64")
 _lib = None
 
 
@@ -103,8 +104,11 @@ def load_library(path: str = None):
     lib.ofl_visualise_workspace_ints.argtypes = [i32]
     lib.ofl_visualise_range_f32.argtypes = [p, i64, i32, p, i64, p, p, p, i32, i32, i32, p]
     lib.ofl_visualise_u8.argtypes = [p, i64, i32, p, i64, i32, i32, p, i32, i32, p, i32, i32, i32, p]
+    lib.ofl_matrix_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    lib.ofl_matrix_fit_f64.argtypes = [p, i64, i32, i32, p, i64, i32, i32, i32, i32, i32, p, p, p, p]
     for name in _SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
+    lib.ofl_matrix_workspace_bytes.restype = ctypes.c_int64
     lib.ofl_splat_tiled_workspace_ints.restype = ctypes.c_int64
     lib.ofl_visualise_workspace_ints.restype = ctypes.c_int64
     lib.ofl_last_kernel_name.restype = ctypes.c_char_p
@@ -1001,6 +1005,30 @@ def visualise(vecs: torch.Tensor, range_max, mode: str, mask: torch.Tensor = Non
         _check(lib.ofl_visualise_u8(_ptr(v), vbs, half, _ptr(m), mbs, int(bool(show_mask)), int(bool(show_mask_borders)),
                                     _ptr(rng), VIS_MODES[mode], int(layout), _ptr(out), n, h, w, _stream(dev)), "ofl_visualise_u8")
     return out
+
+
+# -- Flow.matrix (flow_class.py:1566-1646): ofl_matrix.hip -------------------------------------------------------------------------
+MATRIX_METHODS = {'lms': 0, 'ransac': 1, 'lmeds': 2}
+MATRIX_OK, MATRIX_FEW_POINTS, MATRIX_NO_HYPOTHESIS, MATRIX_REFIT_SINGULAR = 0, 1, 2, 3
+
+
+def matrix_fit(vecs: torch.Tensor, ref: str, mask: torch.Tensor, dof: int, method: str):
+    """The transformation matrix of every image of a flow (ofl_matrix_fit_f64): `dof` 4 / 6 / 8, `method`
+    'lms' / 'ransac' / 'lmeds', `mask` None = every pixel takes part.  Returns (float64 [N,3,3], int32 [N,4]: n_valid, the
+    winner's k, the inlier count, status), both on the HIP device; nothing is read back."""
+    lib, dev = load_library(), device(vecs, mask)
+    n, _, h, w = vecs.shape
+    with _on(dev):
+        v, vbs, half = _vis_flow(vecs, dev, n)
+        m, mbs = (None, 0) if mask is None else _planes(mask, dev, torch.bool, n, "mask")
+        nbytes = int(lib.ofl_matrix_workspace_bytes(n, h, w, int(dof), MATRIX_METHODS[method]))
+        _check(min(nbytes, 0), "ofl_matrix_workspace_bytes")
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        out = torch.empty((n, 3, 3), dtype=torch.float64, device=dev)
+        info = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        _check(lib.ofl_matrix_fit_f64(_ptr(v), vbs, half, 1 if ref == 's' else 0, _ptr(m), mbs, n, h, w, int(dof),
+                                      MATRIX_METHODS[method], _ptr(ws), _ptr(out), _ptr(info), _stream(dev)), "ofl_matrix_fit_f64")
+    return out, info
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1003,6 +1003,37 @@ class Flow(object):
             return _native.visualise(vecs, rng, mode, layout=_native.VIS_INTERLEAVED, **kw).cpu().numpy()
         return _native.visualise(vecs, rng, mode, layout=_native.VIS_PLANES, **kw).to(self._device)
 
+    def matrix(self, dof: int = None, method: str = None, masked: bool = None) -> torch.Tensor:
+        """Fit a transformation matrix to the flow field: `dof` 4 (rotation, translation, scaling), 6 (affine) or 8
+        (homography; default), `method` 'lms', 'ransac' (default) or 'lmeds', `masked` (default True): only pixels inside
+        the flow mask take part.  Returns a float64 tensor N-3-3 on the flow's device.  Fitted on the device by the kernels
+        of ofl_matrix.hip; the reference calls OpenCV's estimators, the numerics here are those of DESIGN.md 3.10.  Raises
+        ValueError for an image with too few usable points (the reference fails with an unrelated TypeError there).  Not
+        differentiable, as in the reference."""
+        dof = 8 if dof is None else dof
+        if dof not in [4, 6, 8]:
+            raise ValueError("Error fitting transformation matrix to flow: Dof needs to be 4, 6 or 8")
+        method = 'ransac' if method is None else method
+        if method not in ['lms', 'ransac', 'lmeds']:
+            raise ValueError("Error fitting transformation matrix to flow: "
+                             "Method needs to be 'lms', 'ransac', or 'lmeds'")
+        masked = True if masked is None else masked
+        if not isinstance(masked, bool):
+            raise TypeError("Error fitting transformation matrix to flow: Masked needs to be boolean")
+        if dof in [4, 6] and method == 'lms':
+            method = 'ransac'
+            warnings.warn("Method 'lms' (least mean squares) not supported for fitting a transformation matrix with 4 "
+                          "or 6 degrees of freedom to the flow - defaulting to 'ransac'")
+        mats, info = _native.matrix_fit(self._fv, self._ref, self._mask if masked else None, dof, method)
+        status = info[:, 3].cpu()                                 # the only host read: N words
+        if bool((status != 0).any()):
+            i = int(torch.nonzero(status)[0])
+            why = {_native.MATRIX_FEW_POINTS: "fewer than {} valid flow vectors".format(dof // 2),
+                   _native.MATRIX_NO_HYPOTHESIS: "no non-degenerate point sample found",
+                   _native.MATRIX_REFIT_SINGULAR: "the inlier points are degenerate"}[int(status[i])]
+            raise ValueError("Error fitting transformation matrix to flow: batch element {}: {}".format(i, why))
+        return mats.to(self._device)
+
     # ------------------------------------------------------------------------------------------
     # composition (flow_class.py:1648-1810)
     # ------------------------------------------------------------------------------------------

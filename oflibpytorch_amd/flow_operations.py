@@ -1,5 +1,5 @@
 """Tensor-level wrappers round the `Flow` methods of the hot path (reference
-``src/oflibpytorch/flow_operations.py:84-277, 339-367, 458-483``): same signatures, 3-D in -> 3-D out."""
+``src/oflibpytorch/flow_operations.py:84-277, 306-367, 458-483``): same signatures, 3-D in -> 3-D out."""
 from typing import Union
 
 import numpy as np
@@ -62,6 +62,12 @@ def visualise_flow(flow, mode: str, range_max: float = None, return_tensor: bool
     """Flow(flow).visualise(mode, range_max=..., return_tensor=...), 3-D in -> 3-D out (flow_operations.py:339-367)"""
     v = Flow(flow).visualise(mode=mode, range_max=range_max, return_tensor=return_tensor)
     return v if len(flow.shape) > 3 else v.squeeze(0)
+
+
+def get_flow_matrix(flow, ref: str, dof: int = None, method: str = None) -> torch.Tensor:
+    """Flow(flow, ref).matrix(dof, method): float64 (N-)3-3, 3-D in -> 3 x 3 out (flow_operations.py:306-336)"""
+    m = Flow(flow, ref).matrix(dof=dof, method=method)
+    return m if len(flow.shape) > 3 else m.squeeze(0)
 
 
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
