@@ -563,6 +563,47 @@ int ofl_matrix_fit_f64(const void* flow, int64_t flow_bs, int32_t flow_half, int
                        int32_t n, int32_t h, int32_t w, int32_t dof, int32_t method, void* workspace, double* out_matrix,
                        int32_t* out_info, void* stream);
 
+/*
+ * Flow.visualise_arrows (flow_class.py:1358-1496) and visualise_flow_arrows (flow_operations.py:370-409): the flow as arrows on a
+ * grid of points.  ofl_arrows.hip.  The reference's NumPy steps are kept bit for bit; the anti-aliased arrow itself is DEFINED in
+ * DESIGN.md 3.11 (three capsules, float64, no fused multiply-add), not OpenCV's LINE_AA.  Grid points: rows
+ * arange(grid_dist / 2, h - 1, grid_dist), columns likewise with w, P per image, row-major.  1 <= grid_dist <= min(h, w) / 2
+ * (so h, w >= 2), else OFL_E_ARG; n <= 65535, n * P < 2^31.  Three calls on one stream, one workspace:
+ *
+ * ofl_arrows_workspace_ints(n, h, w, grid_dist): int32 words of the workspace (header | per-image sums | magnitudes | records | tile counts,
+ *   offsets and cursors), or an OFL_E_* code.
+ *
+ * ofl_arrows_scale_f32 <- `scaling is None` (flow_class.py:1456-1458): the magnitudes of the thresholded flow at the grid points
+ *   (cartToPolar, FMA form), np.percentile(., 99) over all n * P of them (numpy 2.2.6 'linear' in fp32; exact order statistics
+ *   by one block's radix select), *scaling = fp32(grid_dist) / percentile (inf for a percentile of 0).  scaling: DEVICE float[1].
+ *
+ * ofl_arrows_plan <- flow_class.py:1459-1480 up to the drawing: per (image, grid point) the scaled magnitude and vector (fp32),
+ *   drawn iff 0.5 < magnitude <= 2^20, the end point np.round(point +- vector) (float64, half to even; ref_s = 1: 's', arrow
+ *   from the point, thickness 1 whatever `thickness`; 0: 't', arrow to the point), tip length fp32(tip_size) / magnitude, the
+ *   barbs, the colour (`colour` = b | g << 8 | r << 16, or -1: the 'bgr' colour of Flow.visualise for the hue
+ *   uint8(round(mod(angle, 360) / 2)) at full saturation), boxes clipped to the frame; then the number of arrows per 64 x 16
+ *   output tile and the exclusive scan of those counts.  Afterwards workspace[0..1] (int64) = the list entries of all tiles: the
+ *   caller reads it back and sizes `list` from it.  scaling: DEVICE float[1] (ofl_arrows_scale_f32's, or the caller's value);
+ *   1 <= thickness <= 32767; tip_size = fp32(sqrt(thickness) * 3.5).
+ *
+ * ofl_arrows_u8 <- the drawing (flow_class.py:1468-1492): fills the tile lists, then one block per tile paints its pixels in
+ *   registers: background (img uint8, img_layout 0 = [*,3,H,W] planes, 1 = [*,H,W,3], batch stride img_bs in BYTES, 0 broadcasts;
+ *   NULL = white), the tile's arrows in the reference's order (image by image, point by point), each point's pixel set to
+ *   (0, 0, 255) after its arrow, np.round(0.5 * pixel) outside the mask (show_mask), the mask borders black
+ *   (show_mask_borders; the rule of ofl_visualise_u8), one store per pixel.  mask NULL = all True.  list int32[list_ints] with
+ *   list_ints >= workspace[0..1] (a shorter list drops arrows, never writes past it).  out uint8, layout 0 = [N,3,H,W],
+ *   1 = [N,H,W,3], BGR.  `img` is only read.  Bitwise reproducible: integer atomics only, order restored per tile.
+ */
+int64_t ofl_arrows_workspace_ints(int32_t n, int32_t h, int32_t w, int32_t grid_dist);
+int ofl_arrows_scale_f32(const void* flow, int64_t flow_bs, int32_t flow_half, int32_t grid_dist, int32_t* workspace,
+                         float* scaling, int32_t n, int32_t h, int32_t w, void* stream);
+int ofl_arrows_plan(const void* flow, int64_t flow_bs, int32_t flow_half, int32_t ref_s, int32_t grid_dist, const float* scaling,
+                    int32_t colour, int32_t thickness, float tip_size, int32_t* workspace, int32_t n, int32_t h, int32_t w,
+                    void* stream);
+int ofl_arrows_u8(const uint8_t* img, int64_t img_bs, int32_t img_layout, const uint8_t* mask, int64_t mask_bs, int32_t show_mask,
+                  int32_t show_mask_borders, int32_t grid_dist, int32_t* workspace, int32_t* list, int64_t list_ints,
+                  int32_t layout, uint8_t* out, int32_t n, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

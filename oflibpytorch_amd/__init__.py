@@ -2,13 +2,15 @@
 
 Drop-in for the warp / compose hot path of oflibpytorch (`Flow.apply`, `Flow.combine_with` /
 `combine_flows`, `Flow.switch_ref` / `invert`, `apply_flow`, `apply_s_flow`,
-`grid_from_unstructured_data`) and the flow visualisation (`Flow.visualise`, `visualise_flow`) and matrix fitting
-(`Flow.matrix`, `get_flow_matrix`): the
+`grid_from_unstructured_data`) and the flow visualisation (`Flow.visualise`, `visualise_flow`; `Flow.visualise_arrows`, `visualise_flow_arrows`: the
+reference's steps bit for bit, but the arrows by the package's own anti-aliased rasteriser and hue table, not
+OpenCV's; an 's' flow keeps the reference's thickness 1; `img` is never written to and must be uint8; arrows longer than 2^20
+pixels are skipped) and matrix fitting (`Flow.matrix`, `get_flow_matrix`): the
 reference's Python surface (reference `__init__.py:14-18`) over hand-written HIP kernels.  No CPU fallback: see `_native.NativeUnavailable`.
 """
 from .flow_class import Flow, set_revalidate_every_call, get_revalidate_every_call
 from .flow_operations import (combine_flows, switch_flow_ref, invert_flow, valid_target, valid_source, batch_flows,
-                              get_flow_padding, visualise_flow, get_flow_matrix)
+                              get_flow_padding, visualise_flow, visualise_flow_arrows, get_flow_matrix)
 from .utils import (from_matrix, from_transforms, resize_flow, apply_flow, is_zero_flow, get_pure_pytorch,
                     set_pure_pytorch, unset_pure_pytorch, to_numpy, to_tensor, move_axis, apply_s_flow,
                     grid_from_unstructured_data, get_flow_endpoints, threshold_vectors, normalise_coords, track_pts,

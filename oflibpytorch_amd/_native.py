@@ -28,7 +28,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_flow_extents_f32", "ofl_flag_words_or_i32", "ofl_splat_sum_f32", "ofl_warp_bwd_win_f32", "ofl_splat_tiled_win_f32", "ofl_splat_tiled_f16",
             "ofl_warp_bwd_h_f32", "ofl_flow_flags_host", "ofl_host_words_alloc", "ofl_host_words_free", "ofl_flow_from_matrix_f32", "ofl_splat_tiled_fallback_images", "ofl_warp_valid_f32", "ofl_resize_bilinear_f32", "ofl_splat_tile_geometry", "ofl_splat_gather_info", "ofl_last_kernel_name",
             "ofl_visualise_workspace_ints", "ofl_visualise_range_f32", "ofl_visualise_u8",
-            "ofl_matrix_workspace_bytes", "ofl_matrix_fit_f64")
+            "ofl_matrix_workspace_bytes", "ofl_matrix_fit_f64",
+            "ofl_arrows_workspace_ints", "ofl_arrows_scale_f32", "ofl_arrows_plan", "ofl_arrows_u8")
 _lib = None
 
 
@@ -106,8 +107,13 @@ def load_library(path: str = None):
     lib.ofl_visualise_u8.argtypes = [p, i64, i32, p, i64, i32, i32, p, i32, i32, p, i32, i32, i32, p]
     lib.ofl_matrix_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
     lib.ofl_matrix_fit_f64.argtypes = [p, i64, i32, i32, p, i64, i32, i32, i32, i32, i32, p, p, p, p]
+    lib.ofl_arrows_workspace_ints.argtypes = [i32, i32, i32, i32]
+    lib.ofl_arrows_scale_f32.argtypes = [p, i64, i32, i32, p, p, i32, i32, i32, p]
+    lib.ofl_arrows_plan.argtypes = [p, i64, i32, i32, i32, p, i32, i32, f32, p, i32, i32, i32, p]
+    lib.ofl_arrows_u8.argtypes = [p, i64, i32, p, i64, i32, i32, i32, p, p, i64, i32, p, i32, i32, i32, p]
     for name in _SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
+    lib.ofl_arrows_workspace_ints.restype = ctypes.c_int64
     lib.ofl_matrix_workspace_bytes.restype = ctypes.c_int64
     lib.ofl_splat_tiled_workspace_ints.restype = ctypes.c_int64
     lib.ofl_visualise_workspace_ints.restype = ctypes.c_int64
@@ -1029,6 +1035,66 @@ def matrix_fit(vecs: torch.Tensor, ref: str, mask: torch.Tensor, dof: int, metho
         _check(lib.ofl_matrix_fit_f64(_ptr(v), vbs, half, 1 if ref == 's' else 0, _ptr(m), mbs, n, h, w, int(dof),
                                       MATRIX_METHODS[method], _ptr(ws), _ptr(out), _ptr(info), _stream(dev)), "ofl_matrix_fit_f64")
     return out, info
+
+
+# -- Flow.visualise_arrows (flow_class.py:1358-1496): ofl_arrows.hip ---------------------------------------------------------------
+def arrows_scale(vecs: torch.Tensor, grid_dist: int) -> torch.Tensor:
+    """The default `scaling` of Flow.visualise_arrows (flow_class.py:1456-1458) on the device: grid_dist / the 99th percentile
+    of the magnitudes at the grid points of ALL images (ofl_arrows_scale_f32).  Returns a float32 tensor [1] on the HIP device;
+    nothing is read back."""
+    lib, dev = load_library(), device(vecs)
+    n, _, h, w = vecs.shape
+    with _on(dev):
+        v, vbs, half = _vis_flow(vecs, dev, n)
+        ints = int(lib.ofl_arrows_workspace_ints(n, h, w, int(grid_dist)))
+        _check(min(ints, 0), "ofl_arrows_workspace_ints")
+        ws = torch.empty(ints, dtype=torch.int32, device=dev)
+        scaling = torch.empty(1, dtype=torch.float32, device=dev)
+        _check(lib.ofl_arrows_scale_f32(_ptr(v), vbs, half, int(grid_dist), _ptr(ws), _ptr(scaling), n, h, w, _stream(dev)),
+               "ofl_arrows_scale_f32")
+    return scaling
+
+
+def arrows(vecs: torch.Tensor, ref: str, grid_dist: int, scaling, thickness: int, colour=None, img: torch.Tensor = None,
+           img_interleaved: bool = False, mask: torch.Tensor = None, show_mask: bool = False, show_mask_borders: bool = False,
+           layout: int = VIS_PLANES) -> torch.Tensor:
+    """The arrow image of Flow.visualise_arrows (ofl_arrows_plan + ofl_arrows_u8): uint8 BGR [N,3,H,W] (layout
+    VIS_PLANES) or [N,H,W,3] (VIS_INTERLEAVED) on the HIP device.  `scaling`: a float32 device tensor [1] (arrows_scale's) or a
+    number; `colour`: None (hue of the direction) or three 0..255 integers (b, g, r); `img`: None (white) or uint8 [Nb,3,H,W]
+    (`img_interleaved` False) / [Nb,H,W,3] (True) with Nb 1 or N, read only; `mask` None = all True.  One int64 (the length of
+    the tile lists) is read back between the two calls: the lists are sized from the counts."""
+    lib, dev = load_library(), device(vecs, mask)
+    n, _, h, w = vecs.shape
+    g = int(grid_dist)
+    with _on(dev):
+        v, vbs, half = _vis_flow(vecs, dev, n)
+        m, mbs = (None, 0) if mask is None else _planes(mask, dev, torch.bool, n, "mask")
+        if isinstance(scaling, torch.Tensor):
+            sc = scaling.to(device=dev, dtype=torch.float32).reshape(1)
+        else:
+            with np.errstate(over='ignore'):
+                sc = torch.from_numpy(np.array([scaling], dtype=np.float32)).to(dev)      # numpy's cast of the Python scalar
+        im, ibs = None, 0
+        if img is not None:
+            im, ibs = _planes(img, dev, torch.uint8, n, "img")
+        ints = int(lib.ofl_arrows_workspace_ints(n, h, w, g))
+        _check(min(ints, 0), "ofl_arrows_workspace_ints")
+        ws = torch.empty(ints, dtype=torch.int32, device=dev)
+        packed = -1 if colour is None else int(colour[0]) | (int(colour[1]) << 8) | (int(colour[2]) << 16)
+        tip = float(np.float32(np.sqrt(float(thickness)) * 3.5))
+        _check(lib.ofl_arrows_plan(_ptr(v), vbs, half, 1 if ref == 's' else 0, g, _ptr(sc), packed, int(thickness), tip,
+                                   _ptr(ws), n, h, w, _stream(dev)), "ofl_arrows_plan")
+        entries = int(ws[:2].view(torch.int64).item())
+        if entries >= 1 << 31:
+            raise RuntimeError("oflibpytorch_amd: the arrows of this call touch %d tiles, beyond the 2^31 list entries of "
+                               "ofl_arrows_u8 (a smaller scaling or a larger grid_dist draws fewer)" % entries)
+        lst = torch.empty(max(entries, 1), dtype=torch.int32, device=dev)
+        shape = (n, 3, h, w) if layout == VIS_PLANES else (n, h, w, 3)
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+        _check(lib.ofl_arrows_u8(_ptr(im), ibs, 1 if img_interleaved else 0, _ptr(m), mbs, int(bool(show_mask)),
+                                 int(bool(show_mask_borders)), g, _ptr(ws), _ptr(lst), entries, int(layout), _ptr(out), n, h, w,
+                                 _stream(dev)), "ofl_arrows_u8")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1003,6 +1003,81 @@ class Flow(object):
             return _native.visualise(vecs, rng, mode, layout=_native.VIS_INTERLEAVED, **kw).cpu().numpy()
         return _native.visualise(vecs, rng, mode, layout=_native.VIS_PLANES, **kw).to(self._device)
 
+    def visualise_arrows(self, grid_dist: int = None, img: Union[np.ndarray, torch.Tensor] = None,
+                         scaling: Union[float, int] = None, show_mask: bool = None, show_mask_borders: bool = None,
+                         colour: tuple = None, thickness: int = None, return_tensor: bool = None):
+        """The flow as arrows on a grid of points `grid_dist` apart (default 20), over `img` (BGR uint8: NumPy H-W-3 / N-H-W-3
+        or torch 3-H-W / N-3-H-W; default white), scaled by `scaling` (default: the 99th percentile of the arrow lengths over
+        the whole batch equals `grid_dist`), coloured by direction as in :meth:`visualise` or with `colour` (b, g, r), with
+        the area outside the mask halved (`show_mask`) and the mask borders black (`show_mask_borders`).  Returns a uint8
+        tensor N-3-H-W on the flow's device, or a NumPy array N-H-W-3 if `return_tensor` is False.  Computed by the HIP kernels
+        of ofl_arrows.hip.  Everything but the line drawing follows the reference bit for bit; the anti-aliased arrows are
+        those of DESIGN.md 3.11 (own rasteriser and hue table, not OpenCV's).  As in the reference an 's' flow is drawn with
+        thickness 1 whatever `thickness` (which still sizes the tip).  Differences: `img` is never written to, must be uint8,
+        and arrows whose scaled length is not finite or beyond 2^20 pixels are skipped.  Not differentiable."""
+        n, h, w = self.shape
+        # flow_class.py:1395-1446, in the reference's order
+        grid_dist = 20 if grid_dist is None else grid_dist
+        if not isinstance(grid_dist, int):
+            raise TypeError("Error visualising flow arrows: Grid_dist needs to be an integer value")
+        if grid_dist > min(h, w) // 2:
+            print("Warning: grid_dist in visualise_arrows is '{}', which is too large for a flow field of shape "
+                  "({}, {}). grid_dist will be reset to '{}'.".format(grid_dist, h, w, min(h, w) // 2))
+            grid_dist = min(h, w) // 2
+        if not grid_dist > 0:
+            raise ValueError("Error visualising flow arrows: Grid_dist needs to be an integer larger than zero")
+        interleaved = False
+        if img is not None:
+            if not isinstance(img, (np.ndarray, torch.Tensor)):
+                raise TypeError("Error visualising flow arrows: Img needs to be a numpy array or a torch tensor")
+            interleaved = isinstance(img, np.ndarray)
+            if len(img.shape) == 3:
+                img = img[None]
+            want = (h, w, 3) if interleaved else (3, h, w)
+            if len(img.shape) != 4 or img.shape[0] not in (1, n) or tuple(img.shape[1:]) != want:
+                raise ValueError("Error visualising flow arrows: Img needs to have 3 or 4 channels and the same "
+                                 "shape as the flow, including the batch size")
+            if img.dtype not in (np.uint8, torch.uint8):
+                raise TypeError("Error visualising flow arrows: Img needs to be of dtype uint8")
+        if scaling is not None:
+            if not isinstance(scaling, (float, int)):
+                raise TypeError("Error visualising flow arrows: Scaling needs to be a float or an integer")
+            if scaling <= 0:
+                raise ValueError("Error visualising flow arrows: Scaling needs to be larger than zero")
+        show_mask = False if show_mask is None else show_mask
+        show_mask_borders = False if show_mask_borders is None else show_mask_borders
+        return_tensor = True if return_tensor is None else return_tensor
+        if not isinstance(show_mask, bool):
+            raise TypeError("Error visualising flow: Show_mask needs to be boolean")
+        if not isinstance(show_mask_borders, bool):
+            raise TypeError("Error visualising flow: Show_mask_borders needs to be boolean")
+        if not isinstance(return_tensor, bool):
+            raise TypeError("Error visualising flow: Return_tensor needs to be boolean")
+        if colour is not None:
+            if not isinstance(colour, tuple):
+                raise TypeError("Error visualising flow: Colour needs to be a tuple")
+            if len(colour) != 3:
+                raise ValueError("Error visualising flow arrows: Colour list or tuple needs to have length 3")
+            # (OpenCV saturates a colour to 8 bits: round half to even, clamp)
+            colour = tuple(int(c) for c in np.clip(np.rint(np.asarray(colour, np.float64)), 0, 255))
+        thickness = 1 if thickness is None else thickness
+        if not isinstance(thickness, int):
+            raise TypeError("Error visualising flow: Thickness needs to be an integer")
+        if thickness <= 0:
+            raise ValueError("Error visualising flow: Thickness needs to be a integer larger than zero")
+        if thickness > 32767:                                     # (OpenCV's MAX_THICKNESS: the reference fails inside cv2)
+            raise ValueError("Error visualising flow: Thickness needs to be at most 32767")
+        self._require_finite("Error visualising flow arrows: ")
+        vecs, mask = self._fv, self._mask            # (no mask: all True, never materialised)
+        if isinstance(img, np.ndarray):
+            img = torch.from_numpy(np.ascontiguousarray(img))    # (read only: the kernels never write to it)
+        if scaling is None:
+            scaling = _native.arrows_scale(vecs, grid_dist)
+        out = _native.arrows(vecs, self._ref, grid_dist, scaling, thickness, colour=colour, img=img, img_interleaved=interleaved,
+                             mask=mask, show_mask=show_mask and mask is not None, show_mask_borders=show_mask_borders,
+                             layout=_native.VIS_PLANES if return_tensor else _native.VIS_INTERLEAVED)
+        return out.to(self._device) if return_tensor else out.cpu().numpy()
+
     def matrix(self, dof: int = None, method: str = None, masked: bool = None) -> torch.Tensor:
         """Fit a transformation matrix to the flow field: `dof` 4 (rotation, translation, scaling), 6 (affine) or 8
         (homography; default), `method` 'lms', 'ransac' (default) or 'lmeds', `masked` (default True): only pixels inside
@@ -1257,6 +1332,6 @@ def _combine_plan(mode: int, self_ref: str, other_ref: str, out_ref: str) -> _Co
 
 # the public methods that read a flow's flag word: each starts a new validation epoch under set_revalidate_every_call(True)
 for _name in ('apply', 'track', 'switch_ref', 'invert', 'valid_target', 'valid_source', 'get_padding', 'is_zero', 'combine_with',
-              'combine', 'visualise'):
+              'combine', 'visualise', 'visualise_arrows'):
     setattr(Flow, _name, _public(getattr(Flow, _name)))
 del _name

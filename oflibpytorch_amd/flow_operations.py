@@ -1,5 +1,5 @@
 """Tensor-level wrappers round the `Flow` methods of the hot path (reference
-``src/oflibpytorch/flow_operations.py:84-277, 306-367, 458-483``): same signatures, 3-D in -> 3-D out."""
+``src/oflibpytorch/flow_operations.py:84-277, 306-409, 458-483``): same signatures, 3-D in -> 3-D out."""
 from typing import Union
 
 import numpy as np
@@ -62,6 +62,14 @@ def visualise_flow(flow, mode: str, range_max: float = None, return_tensor: bool
     """Flow(flow).visualise(mode, range_max=..., return_tensor=...), 3-D in -> 3-D out (flow_operations.py:339-367)"""
     v = Flow(flow).visualise(mode=mode, range_max=range_max, return_tensor=return_tensor)
     return v if len(flow.shape) > 3 else v.squeeze(0)
+
+
+def visualise_flow_arrows(flow, ref: str, grid_dist: int = None, img=None, scaling: Union[float, int] = None, colour: tuple = None,
+                          thickness: int = None, return_tensor: bool = None):
+    """Flow(flow, ref).visualise_arrows(...), 3-D in -> 3-D out (flow_operations.py:370-409)"""
+    a = Flow(flow, ref).visualise_arrows(grid_dist=grid_dist, img=img, scaling=scaling, colour=colour, thickness=thickness,
+                                         return_tensor=return_tensor)
+    return a if len(flow.shape) > 3 else a.squeeze(0)
 
 
 def get_flow_matrix(flow, ref: str, dof: int = None, method: str = None) -> torch.Tensor:
