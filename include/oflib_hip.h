@@ -604,6 +604,43 @@ int ofl_arrows_u8(const uint8_t* img, int64_t img_bs, int32_t img_layout, const 
                   int32_t show_mask_borders, int32_t grid_dist, int32_t* workspace, int32_t* list, int64_t list_ints,
                   int32_t layout, uint8_t* out, int32_t n, int32_t h, int32_t w, void* stream);
 
+/*
+ * The triangle-mesh interpolator (ofl_mesh.hip): apply_flow(ref='s') and track_pts(ref='t') with PURE_PYTORCH unset
+ * and set_mesh_interpolation() on -- where the reference calls scipy.interpolate.griddata (utils.py:577-600, :1020-1032).  Vertices:
+ * pixel (i, j) of flow image b at (j + flow_sign * u, i + flow_sign * v) in float64; usable iff mask (NULL = all True) is set there and
+ * both coordinates are finite.  Quad q = i * (w - 1) + j with four usable vertices gives triangles 2 q and 2 q + 1, split along the
+ * diagonal the in-circle test keeps (a tie keeps (i, j)-(i + 1, j + 1)); zero-area triangles are dropped.  A query takes the barycentric
+ * interpolation of the lowest-numbered triangle that contains it (edges included, exact signs of the float64 edge functions) or 0.
+ * h, w >= 2, h * w < 2^30, nf <= 65535.  flow fp32 [nf,2,h,w] (flow_bs elements between images), mask uint8 [nf,h,w].
+ *
+ * ofl_mesh_workspace_ints(nf, h, w, points): int32 words of the workspace (header | tile offsets, counts, cursors), or an OFL_E_* code;
+ *   points = 0: pixel queries over 64 x 16 tiles (ofl_mesh_apply), 1: point queries over 8 x 8 tiles (ofl_mesh_points).
+ *
+ * ofl_mesh_plan: the number of quads whose box touches each tile and the exclusive scan of those counts.  Afterwards workspace[0..1]
+ *   (int64) = the list entries of all tiles: the caller reads it back and sizes `list` from it.  Nothing is capped: a quad is listed in
+ *   every tile its box touches.
+ *
+ * ofl_mesh_apply: fills the tile lists, then one block per tile: every pixel keeps the lowest triangle that contains its centre and
+ *   interpolates the c channels of src ([*,c,h,w] fp32, or uint8 with src_u8 = 1; src_bs elements between images, 0 broadcasts; nf is
+ *   1 or n) from that triangle's three source pixels; the float64 value is rounded to fp32, then by round_mode (OFL_ROUND_*; uint8 needs
+ *   OFL_ROUND_U8).  dst [n,c,h,w] of src's type; inside (optional) uint8 [n,h,w] 1 where a triangle was found; owner (optional) int32
+ *   [n,h,w] its number or -1.  list int32[list_ints] with list_ints >= workspace[0..1] (a shorter list drops quads, never writes past
+ *   it).  Bitwise reproducible: the only atomics are integer minima and list cursors, and no result depends on the list's order.
+ *
+ * ofl_mesh_points: fills the lists of a points = 1 plan, then one thread per point: pts float64 [*,m,2] (y, x; pts_bs doubles between
+ *   images, 0 broadcasts) -> vecs float64 [nf,m,2] (y, x) the interpolated flow vector (0 outside every triangle and outside
+ *   [0, w - 1] x [0, h - 1]) and inside uint8 [nf,m].
+ */
+int64_t ofl_mesh_workspace_ints(int32_t nf, int32_t h, int32_t w, int32_t points);
+int ofl_mesh_plan(const float* flow, int64_t flow_bs, float flow_sign, const uint8_t* mask, int64_t mask_bs, int32_t points,
+                  int32_t* workspace, int32_t nf, int32_t h, int32_t w, void* stream);
+int ofl_mesh_apply(const float* flow, int64_t flow_bs, float flow_sign, const uint8_t* mask, int64_t mask_bs, const void* src,
+                   int64_t src_bs, int32_t src_u8, int32_t round_mode, int32_t* workspace, int32_t* list, int64_t list_ints, void* dst,
+                   uint8_t* inside, int32_t* owner, int32_t nf, int32_t n, int32_t c, int32_t h, int32_t w, void* stream);
+int ofl_mesh_points(const float* flow, int64_t flow_bs, float flow_sign, const uint8_t* mask, int64_t mask_bs, const double* pts,
+                    int64_t pts_bs, int32_t* workspace, int32_t* list, int64_t list_ints, double* vecs, uint8_t* inside, int32_t nf,
+                    int32_t m, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ from .flow_operations import (combine_flows, switch_flow_ref, invert_flow, valid
 from .utils import (from_matrix, from_transforms, resize_flow, apply_flow, is_zero_flow, get_pure_pytorch,
                     set_pure_pytorch, unset_pure_pytorch, to_numpy, to_tensor, move_axis, apply_s_flow,
                     grid_from_unstructured_data, get_flow_endpoints, threshold_vectors, normalise_coords, track_pts,
-                    set_half_flow_outputs, get_half_flow_outputs)
+                    set_half_flow_outputs, get_half_flow_outputs, set_mesh_interpolation, get_mesh_interpolation)
 from ._native import NativeUnavailable
 
 __version__ = "0.1.0"

@@ -29,7 +29,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_warp_bwd_h_f32", "ofl_flow_flags_host", "ofl_host_words_alloc", "ofl_host_words_free", "ofl_flow_from_matrix_f32", "ofl_splat_tiled_fallback_images", "ofl_warp_valid_f32", "ofl_resize_bilinear_f32", "ofl_splat_tile_geometry", "ofl_splat_gather_info", "ofl_last_kernel_name",
             "ofl_visualise_workspace_ints", "ofl_visualise_range_f32", "ofl_visualise_u8",
             "ofl_matrix_workspace_bytes", "ofl_matrix_fit_f64",
-            "ofl_arrows_workspace_ints", "ofl_arrows_scale_f32", "ofl_arrows_plan", "ofl_arrows_u8")
+            "ofl_arrows_workspace_ints", "ofl_arrows_scale_f32", "ofl_arrows_plan", "ofl_arrows_u8",
+            "ofl_mesh_workspace_ints", "ofl_mesh_plan", "ofl_mesh_apply", "ofl_mesh_points")
 _lib = None
 
 
@@ -111,9 +112,14 @@ def load_library(path: str = None):
     lib.ofl_arrows_scale_f32.argtypes = [p, i64, i32, i32, p, p, i32, i32, i32, p]
     lib.ofl_arrows_plan.argtypes = [p, i64, i32, i32, i32, p, i32, i32, f32, p, i32, i32, i32, p]
     lib.ofl_arrows_u8.argtypes = [p, i64, i32, p, i64, i32, i32, i32, p, p, i64, i32, p, i32, i32, i32, p]
+    lib.ofl_mesh_workspace_ints.argtypes = [i32, i32, i32, i32]
+    lib.ofl_mesh_plan.argtypes = [p, i64, f32, p, i64, i32, p, i32, i32, i32, p]
+    lib.ofl_mesh_apply.argtypes = [p, i64, f32, p, i64, p, i64, i32, i32, p, p, i64, p, p, p, i32, i32, i32, i32, i32, p]
+    lib.ofl_mesh_points.argtypes = [p, i64, f32, p, i64, p, i64, p, p, i64, p, p, i32, i32, i32, i32, p]
     for name in _SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     lib.ofl_arrows_workspace_ints.restype = ctypes.c_int64
+    lib.ofl_mesh_workspace_ints.restype = ctypes.c_int64
     lib.ofl_matrix_workspace_bytes.restype = ctypes.c_int64
     lib.ofl_splat_tiled_workspace_ints.restype = ctypes.c_int64
     lib.ofl_visualise_workspace_ints.restype = ctypes.c_int64
@@ -1095,6 +1101,64 @@ def arrows(vecs: torch.Tensor, ref: str, grid_dist: int, scaling, thickness: int
                                  int(bool(show_mask_borders)), g, _ptr(ws), _ptr(lst), entries, int(layout), _ptr(out), n, h, w,
                                  _stream(dev)), "ofl_arrows_u8")
     return out
+
+
+# -- the triangle-mesh interpolator: ofl_mesh.hip -------------------------------------------------------------------
+def _mesh_plan(lib, dev, v, vbs, sign, m, mbs, points, nf, h, w):
+    """ofl_mesh_plan, the read-back of the lists' length and the list: (workspace, list, entries)"""
+    ints = int(lib.ofl_mesh_workspace_ints(nf, h, w, points))
+    _check(min(ints, 0), "ofl_mesh_workspace_ints")
+    ws = torch.empty(ints, dtype=torch.int32, device=dev)
+    _check(lib.ofl_mesh_plan(_ptr(v), vbs, sign, _ptr(m), mbs, points, _ptr(ws), nf, h, w, _stream(dev)), "ofl_mesh_plan")
+    entries = int(ws[:2].view(torch.int64).item())
+    return ws, torch.empty(max(entries, 1), dtype=torch.int32, device=dev), entries
+
+
+def _mesh_flow(flow, mask, dev):
+    nf = flow.shape[0]
+    v, vbs = _planes(flow.detach(), dev, torch.float32, nf, "flow")
+    m, mbs = (None, 0) if mask is None else _planes(mask, dev, torch.bool, nf, "mask")
+    return v, (v.stride(0) if nf > 1 else 0), m, (0 if m is None or nf == 1 else m.stride(0))
+
+
+def mesh_apply(flow, data, *, mask=None, flow_sign=1.0, round_mode=ROUND_NONE, want_inside=False, want_owner=False):
+    """ofl_mesh_plan + ofl_mesh_apply: flow [Nf,2,H,W] 's', data [Nd,C,H,W] (uint8 stays uint8 with ROUND_U8, everything else goes
+    through fp32), mask [Nf,H,W] bool or None; Nf, Nd in {1, N}.  -> (out [N,C,H,W] fp32 / uint8, inside uint8 [N,H,W] | None,
+    owner int32 [N,H,W] | None) on the HIP device.  No gradient: the reference's griddata path has none."""
+    lib, dev = load_library(), device(flow, data, mask)
+    nf, _, h, w = flow.shape
+    n, c = max(nf, data.shape[0]), data.shape[1]
+    u8 = data.dtype == torch.uint8 and round_mode == ROUND_U8
+    with _on(dev):
+        v, vbs, m, mbs = _mesh_flow(flow, mask, dev)
+        d, dbs = _planes(data.detach(), dev, torch.uint8 if u8 else torch.float32, n, "data")
+        ws, lst, entries = _mesh_plan(lib, dev, v, vbs, float(flow_sign), m, mbs, 0, nf, h, w)
+        out = torch.empty((n, c, h, w), dtype=d.dtype, device=dev)
+        inside = torch.empty((n, h, w), dtype=torch.uint8, device=dev) if want_inside else None
+        owner = torch.empty((n, h, w), dtype=torch.int32, device=dev) if want_owner else None
+        _check(lib.ofl_mesh_apply(_ptr(v), vbs, float(flow_sign), _ptr(m), mbs, _ptr(d), dbs, int(u8), int(round_mode), _ptr(ws),
+                                  _ptr(lst), entries, _ptr(out), _ptr(inside), _ptr(owner), nf, n, c, h, w, _stream(dev)),
+               "ofl_mesh_apply")
+    return out, inside, owner
+
+
+def mesh_points(flow, pts, *, mask=None, flow_sign=-1.0):
+    """ofl_mesh_plan + ofl_mesh_points: flow [N,2,H,W], pts [N or 1,M,2] (y, x) of any real dtype -> (vecs float64 [N,M,2] (y, x),
+    inside uint8 [N,M]): the flow interpolated over the mesh of the vertices grid + flow_sign * flow, 0 where no triangle holds
+    the point."""
+    lib, dev = load_library(), device(flow, pts, mask)
+    nf, _, h, w = flow.shape
+    mpts = pts.shape[1]
+    with _on(dev):
+        v, vbs, m, mbs = _mesh_flow(flow, mask, dev)
+        p, pbs = _planes(pts.detach(), dev, torch.float64, nf, "pts")
+        vecs = torch.zeros((nf, mpts, 2), dtype=torch.float64, device=dev)
+        inside = torch.zeros((nf, mpts), dtype=torch.uint8, device=dev)
+        if mpts > 0:
+            ws, lst, entries = _mesh_plan(lib, dev, v, vbs, float(flow_sign), m, mbs, 1, nf, h, w)
+            _check(lib.ofl_mesh_points(_ptr(v), vbs, float(flow_sign), _ptr(m), mbs, _ptr(p), pbs, _ptr(ws), _ptr(lst), entries,
+                                       _ptr(vecs), _ptr(inside), nf, mpts, h, w, _stream(dev)), "ofl_mesh_points")
+    return vecs, inside
 
 
 # ------------------------------------------------------------------------------------------------

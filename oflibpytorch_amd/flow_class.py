@@ -23,7 +23,7 @@ from . import _native, distributed
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
-                    interpolate_bilinear)
+                    interpolate_bilinear, _mesh_mode)
 
 FlowAlias = 'Flow'
 _VALID_THR = 0.99999   # flow_class.py:922
@@ -765,8 +765,7 @@ class Flow(object):
         subtracted inside the kernel (modes 1 't' / 2 's': target `flow - self`; `tmask` / the two channel masks carry
         m_flow & m_self).  `mask_chan_b` ('s' only; the padded batch-1-target case of `_warp_padded`): the batch-1 flow mask
         that goes into the mask channel instead of this flow's own, and keeps an all-zero flow's result at batch 1."""
-        if self._ref == 's' and not get_pure_pytorch():
-            _griddata_unavailable("Flow.apply(ref='s')")
+        mesh = self._ref == 's' and _mesh_mode("Flow.apply(ref='s')")
         batch_flags = self._batch_flags()                                             # (one look at the cached word for both tests)
         if batch_flags & _native.FLAG_NONFINITE:                                      # utils.py:98
             raise ValueError("Error applying flow to a target: Input contains NaN, Inf or -Inf values")
@@ -794,7 +793,9 @@ class Flow(object):
                     warped = torch.clamp(warped, 0, 255)
             return warped, valid, None
         dflags = None
-        if self._ref == 't':
+        if mesh:
+            warped, valid = self._warp_mesh(t, tmask, need_valid, consider_mask, round_mode, flow_sign, data_sign, t_minus, mask_chan_b)
+        elif self._ref == 't':
             warped, valid, _, _ = _native.warp_bwd(self._fv, t, src_mask=tmask,
                                                    flow_mask=self._mask if need_valid else None,
                                                    want_valid=need_valid, round_mode=round_mode, src_b=t_minus,
@@ -811,6 +812,34 @@ class Flow(object):
             warped, valid = res[0], res[1]
             dflags = res[4] if want_f else None
         return warped.to(self._device), (None if valid is None else valid.to(self._device)), dflags
+
+    def _warp_mesh(self, t, tmask, need_valid, consider_mask, round_mode, flow_sign, data_sign, t_minus, mask_chan_b):
+        """`_warp` of an 's' flow with PURE_PYTORCH unset and the mesh interpolator on: the reference's own
+        composition (flow_class.py:878-934) around `apply_flow` -- the target as floats, the mask (target's AND flow's) as one
+        more channel, interpolated together, the channel thresholded at 0.99999.  Rounding follows on the fp32 result (:943-946).
+        Nothing here is differentiable, as in the reference (utils.py:577-600 goes through NumPy)."""
+        dev = self._device
+        data = t.detach().to(dev).float()
+        if t_minus is not None:
+            data = data - t_minus.detach().to(dev).float()
+        if data_sign != 1.0:
+            data = data * data_sign
+        if need_valid:
+            m = torch.ones((t.shape[0],) + tuple(t.shape[2:]), dtype=torch.bool, device=dev) if tmask is None else tmask.to(dev)
+            m = m & (self.mask if mask_chan_b is None else mask_chan_b.to(dev))                  # :895
+            if m.shape[0] != data.shape[0]:                                                      # :896-897
+                data = data.expand(m.shape[0], -1, -1, -1)
+            data = torch.cat((data, m.unsqueeze(1).float()), dim=1)
+        out = _native.mesh_apply(self._vecs, data, mask=self.mask if consider_mask and self._mask is not None else None,
+                                 flow_sign=flow_sign)[0].to(dev)
+        valid = None
+        if need_valid:
+            valid, out = out[:, -1] > _VALID_THR, out[:, :-1]
+        if round_mode:
+            out = torch.round(out)
+            if round_mode == _native.ROUND_U8:
+                out = torch.clamp(out, 0, 255)
+        return out, valid
 
     # ------------------------------------------------------------------------------------------
     # track (flow_class.py:961-1020)
@@ -908,11 +937,16 @@ class Flow(object):
         """apply_flow(sign * vecs, mask.float(), 's', mask if consider_mask else None) == 1 (flow_class.py:1116-1118,
         1165-1169): the flow mask splatted as data, through the kernels' mask channel so that "every contributor
         valid" is exactly 1 whatever order the accumulation ran in."""
-        if not get_pure_pytorch():
-            _griddata_unavailable("valid_target / valid_source")
+        mesh = _mesh_mode("valid_target / valid_source")
         self._require_finite("Error applying flow to a target: ")
         if self._all_zero(_native.FLAG_NZ_THR):                      # apply_flow's early exit: the mask itself
             return self.mask.clone()
+        if mesh:
+            # the same composition through the mesh interpolator: the mask as fp32 data; a pixel whose
+            # triangle has three valid corners gets float32(w0 + w1 + w2) = 1
+            area = _native.mesh_apply(self._vecs, self.mask.unsqueeze(1).float(), flow_sign=sign,
+                                      mask=self._mask if consider_mask else None)[0]
+            return (area[:, 0] == 1).to(self._device)
         dummy = self._vecs[:, :1]
         _, mch, _, _ = _native.splat_fwd(self._vecs, dummy, flow_sign=sign, chan_mask_a=self._mask,
                                          weight_mask=self._mask if consider_mask else None, occlude=True,
@@ -1167,6 +1201,8 @@ class Flow(object):
             warped, valid, dflags = self._warp(flow._vecs, flow._mask, True, True, t_minus=self._vecs)
             return Flow._wrap(warped, 's', valid, self._device, flags=dflags, made_from=(flow._fv, flow._mask, self._mask))
         if not get_pure_pytorch():
+            # the reference resamples (vectors, mask) at the float positions grid - flow of a SECOND flow with a griddata call of its own
+            # (:1776-1796): a whole-frame point query over C channels, which the mesh kernels do not have
             _griddata_unavailable("combine_with(mode=2, ref='t')")
         return flow._minus_applied(flow, self.invert().apply(self))                  # :1773  flow - flow.apply(...)
 

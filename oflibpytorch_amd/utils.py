@@ -34,7 +34,8 @@ def set_pure_pytorch(warn: bool = None):
 
 def unset_pure_pytorch(warn: bool = None):
     """utils.py:54-69.  The flag is kept for API compatibility; the griddata (Delaunay, CPU-only) variants of
-    the 's'-reference operations are outside the accelerated path and raise NotImplementedError."""
+    the 's'-reference operations are outside the accelerated path and raise NotImplementedError -- unless
+    `set_mesh_interpolation()` is on, which runs the package's own triangle-mesh interpolator in their place."""
     global PURE_PYTORCH
     PURE_PYTORCH = False
     if bool(warn):
@@ -56,6 +57,33 @@ def set_half_flow_outputs(on: bool = True):
     Off by default: the reference up-casts on entry and returns fp32 flows (utils.py:95, 118)."""
     global HALF_FLOW_OUTPUTS
     HALF_FLOW_OUTPUTS = bool(on)
+
+
+MESH_INTERPOLATION = False  # extension (off: the griddata variants raise NotImplementedError): see set_mesh_interpolation
+
+
+def get_mesh_interpolation() -> bool:
+    return MESH_INTERPOLATION
+
+
+def set_mesh_interpolation(on: bool = True):
+    """Extension: when on AND `unset_pure_pytorch()` is in force, the operations the reference hands to
+    `scipy.interpolate.griddata(..., method='linear')` (`apply_flow(ref='s')`, `track_pts(ref='t')` and what is built on them) run
+    the package's own triangle-mesh interpolator on the HIP device (`ofl_mesh.hip`): piecewise-linear over the
+    warped pixel grid's own quads, each split along its locally Delaunay diagonal.  It equals griddata's result only while the
+    warped grid's Delaunay triangulation IS that mesh (smooth flows), fills no convex hull, bridges no masked hole, and is not
+    differentiable.  Off by default (the gates raise NotImplementedError); no effect while PURE_PYTORCH is set."""
+    global MESH_INTERPOLATION
+    MESH_INTERPOLATION = bool(on)
+
+
+def _mesh_mode(what: str) -> bool:
+    """True: the mesh interpolator takes `what`; False: the splat does (PURE_PYTORCH); raises when neither is available."""
+    if get_pure_pytorch():
+        return False
+    if not get_mesh_interpolation():
+        _griddata_unavailable(what)
+    return True
 
 
 def _griddata_unavailable(what: str):
@@ -433,9 +461,10 @@ def apply_flow(flow, target: torch.Tensor, ref: str, mask=None) -> torch.Tensor:
     if ref == 't':
         out = _native.warp_bwd(flow, t, round_mode=rm, out_uint8=True)[0]
     else:
-        if not get_pure_pytorch():
-            _griddata_unavailable("apply_flow(ref='s')")
-        out = _native.splat_fwd(flow, t, weight_mask=mask, occlude=True, round_mode=rm)[0]
+        if _mesh_mode("apply_flow(ref='s')"):
+            out = _native.mesh_apply(flow, t, mask=mask, round_mode=rm)[0]          # (no grad_fn: utils.py:577-600 goes through NumPy)
+        else:
+            out = _native.splat_fwd(flow, t, weight_mask=mask, occlude=True, round_mode=rm)[0]
     out = out.to(flow.device)
     if out.shape[0] == 1:
         if dims == 2:
@@ -549,12 +578,18 @@ def track_pts(flow, ref: str, pts: torch.Tensor, int_out: bool = None) -> torch.
 
     moved = points
     if any(wd & _native.FLAG_NZ_THR for wd in words):                           # (all below the threshold: nothing moves, :988-989)
-        field = flow
-        if ref == 't':
-            if not get_pure_pytorch():
-                _griddata_unavailable("track_pts(ref='t')")
+        field, mesh = flow, ref == 't' and _mesh_mode("track_pts(ref='t')")
+        if ref == 't' and not mesh:
             field = _native.splat_fwd(flow, flow, flow_sign=-1.0, occlude=False)[0].to(flow.device)
-        if points.dtype.is_floating_point:
+        if mesh:
+            # utils.py:1020-1035: the flow interpolated at the points over the mesh of the start points grid - flow (float64), added
+            # to the points in their own dtype by the reference's own in-place `+=` (which refuses integer points, as there);
+            # a point no triangle holds comes back as (0, 0).  The vectors are constants: only the points carry a gradient.
+            vecs, inside = _native.mesh_points(flow, points, flow_sign=-1.0)
+            moved = points.clone()
+            moved += vecs.to(flow.device)
+            moved = torch.where(inside.to(flow.device).bool()[..., None], moved, torch.zeros_like(moved))
+        elif points.dtype.is_floating_point:
             from . import _autograd
             moved = _autograd.sample_pts(field, points.float()).to(flow.device)  # (a point whose sample is NaN comes back as 0)
         else:
