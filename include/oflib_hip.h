@@ -397,6 +397,36 @@ int ofl_warp_bwd_h_f32(const float* flow, int64_t flow_bs, float flow_sign,
                        float* dst, uint8_t* valid,
                        int32_t n, int32_t h, int32_t w, void* stream);
 
+/*
+ * FEATURE TENSORS STORED IN fp16 / bf16 (Flow.apply / apply_flow 't' of an N-C-H-W tensor held in half precision, as flow
+ * networks under autocast hold them).  The reference converts the target to fp32, samples in fp32 and converts the result
+ * back (utils.py:512-618: `target.float()` -> grid_sample -> `result.to(target_dtype)`); so does this entry point, inside
+ * the kernel: the 16-bit planes are up-converted at the load (exact), the fp32 arithmetic is that of ofl_warp_bwd_f32 in
+ * the same order, and the result is rounded ONCE, to nearest even, at the store (NaN -> a NaN, +-inf and overflow -> +-inf,
+ * as `Tensor.to`).  Bit-identical to converting, calling ofl_warp_bwd_f32 and converting back, without the two fp32 copies
+ * (2 + 2 instead of ~20 bytes per element through HBM).
+ *
+ *   ofl_warp_bwd_x16      the arguments of ofl_warp_bwd_f32, with src [*,C,H,W] and dst [N,C,H,W] planes of `dtype`
+ *                         (OFL_X16_HALF: IEEE binary16, OFL_X16_BFLOAT: bfloat16) at 2-byte alignment, any W; `flow` fp32.
+ *                         src_mask / flow_mask / valid as there; batch strides of 0 broadcast.  The PLAIN warp only: with
+ *                         src_b, addend, flow_flags / src_flags / dst_flags or a rounding mode, off the automatic
+ *                         OFL_OPT_WARP_PATH, or beyond the staged kernels (W < 4, H < 2, H*W >= 2^24) it returns
+ *                         OFL_E_UNSUPPORTED and launches nothing: convert and call ofl_warp_bwd_f32 (a flow window:
+ *                         ofl_warp_bwd_win_f32).  OFL_E_ARG for another dtype.  ofl_last_kernel_name() then names an
+ *                         instantiation on `half_t` / `bf16_t`.
+ */
+#define OFL_X16_HALF 0
+#define OFL_X16_BFLOAT 1
+int ofl_warp_bwd_x16(const float* flow, int64_t flow_bs, float flow_sign,
+                     const void* src, int64_t src_bs,
+                     const void* src_b, int64_t src_b_bs,
+                     const uint8_t* src_mask, int64_t src_mask_bs,
+                     const uint8_t* flow_mask, int64_t flow_mask_bs,
+                     const void* addend, int64_t addend_bs, float a_sign, float g_sign,
+                     void* dst, uint8_t* valid,
+                     int32_t* flow_flags, int32_t* src_flags, int32_t* dst_flags,
+                     int32_t n, int32_t c, int32_t h, int32_t w,
+                     int32_t round_mode, int32_t dtype, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------------

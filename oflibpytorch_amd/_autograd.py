@@ -28,8 +28,20 @@ class WarpFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flow, src, addend, src_b, kw):
         d = lambda t: None if t is None else t.detach()
-        with _native._on(_native.device(flow, src)):
-            res = _native._warp_bwd_raw(d(flow), d(src), addend=d(addend), src_b=d(src_b), **kw)
+        kw = dict(kw)
+        res = None
+        if kw.pop("keep16", False):
+            # a feature tensor stored in fp16 / bf16: the native 16-bit launch, and the 16-BIT source is what is saved (the
+            # backward up-converts it transiently for the fp32 backward kernels); a launch the library declines is converted
+            # here, so that the output has the source's dtype either way
+            res = _native._warp_bwd_x16(d(flow), d(src), addend=d(addend), src_b=d(src_b), **kw)
+            if res is None:
+                with _native._on(_native.device(flow, src)):
+                    res = _native._warp_bwd_raw(d(flow), d(src).float(), addend=d(addend), src_b=d(src_b), **kw)
+                res = (res[0].to(src.dtype),) + tuple(res[1:])
+        if res is None:
+            with _native._on(_native.device(flow, src)):
+                res = _native._warp_bwd_raw(d(flow), d(src), addend=d(addend), src_b=d(src_b), **kw)
         ctx.save_for_backward(flow, src, src_b)
         ctx.addend_meta = None if addend is None else (addend.shape[0], addend.device, addend.dtype)
         ctx.signs = (float(kw.get("flow_sign", 1.0)), float(kw.get("a_sign", 1.0)), float(kw.get("g_sign", 1.0)))
@@ -67,12 +79,15 @@ def warp(flow, src, **kw):
     if int(kw.get("round_mode", 0)) != 0:
         d = lambda t: None if t is None else t.detach()
         kw = dict(kw)
+        kw.pop("keep16", None)
         kw["addend"], kw["src_b"] = d(kw.get("addend")), d(kw.get("src_b"))
         with _native._on(_native.device(flow, src)):
             return _native._warp_bwd_raw(flow.detach(), src.detach(), **kw)
     kw = dict(kw)
     addend, src_b = kw.pop("addend", None), kw.pop("src_b", None)
     kw.pop("out_uint8", None)
+    if kw.get("keep16") and not (addend is None and src_b is None):
+        kw.pop("keep16")
     if src.dtype == torch.uint8:          # (only the flow can want a gradient: the backward kernel reads float planes)
         src = src.float()
     return WarpFn.apply(flow, src, addend, src_b, kw)

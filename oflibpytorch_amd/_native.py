@@ -30,7 +30,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_visualise_workspace_ints", "ofl_visualise_range_f32", "ofl_visualise_u8",
             "ofl_matrix_workspace_bytes", "ofl_matrix_fit_f64",
             "ofl_arrows_workspace_ints", "ofl_arrows_scale_f32", "ofl_arrows_plan", "ofl_arrows_u8",
-            "ofl_mesh_workspace_ints", "ofl_mesh_plan", "ofl_mesh_apply", "ofl_mesh_points")
+            "ofl_mesh_workspace_ints", "ofl_mesh_plan", "ofl_mesh_apply", "ofl_mesh_points",
+            "ofl_warp_bwd_x16")
 _lib = None
 
 
@@ -116,6 +117,8 @@ def load_library(path: str = None):
     lib.ofl_mesh_plan.argtypes = [p, i64, f32, p, i64, i32, p, i32, i32, i32, p]
     lib.ofl_mesh_apply.argtypes = [p, i64, f32, p, i64, p, i64, i32, i32, p, p, i64, p, p, p, i32, i32, i32, i32, i32, p]
     lib.ofl_mesh_points.argtypes = [p, i64, f32, p, i64, p, i64, p, p, i64, p, p, i32, i32, i32, i32, p]
+    lib.ofl_warp_bwd_x16.argtypes = [p, i64, f32, p, i64, p, i64, p, i64, p, i64, p, i64, f32, f32, p, p, p, p, p,
+                                     i32, i32, i32, i32, i32, i32, p]
     for name in _SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     lib.ofl_arrows_workspace_ints.restype = ctypes.c_int64
@@ -469,10 +472,58 @@ def _warp_bwd_lean(flow, src, flow_sign=1.0, src_mask=None, flow_mask=None, want
     return dst, valid, None, None
 
 
+_X16_DTYPES = {torch.float16: 0, torch.bfloat16: 1}       # OFL_X16_HALF, OFL_X16_BFLOAT
+
+
+def _warp_bwd_x16(flow, src, *, flow_sign=1.0, src_mask=None, flow_mask=None, want_valid=False, addend=None, a_sign=1.0,
+                  g_sign=1.0, round_mode=ROUND_NONE, want_flags=False, want_src_flags=False, want_dst_flags=False,
+                  src_b=None, out_uint8=False):
+    """ofl_warp_bwd_x16: a feature tensor stored in fp16 / bf16 warped from and to its 16-bit planes (fp32 warper, fp32
+    arithmetic, one rounding at the store); dst has the source's dtype.  None when the launch is not of that kind or the
+    library declines it: the caller up-converts and takes the fp32 kernel."""
+    if (src.dtype not in _X16_DTYPES or src.device.type != 'cuda' or addend is not None or src_b is not None
+            or round_mode != ROUND_NONE or want_flags or want_dst_flags):
+        return None
+    lib, dev = load_library(), device(flow, src)
+    c, h, w = src.shape[1:]
+    n = max(flow.shape[0], src.shape[0], 1 if src_mask is None else src_mask.shape[0], 1 if flow_mask is None else flow_mask.shape[0])
+    with _on(dev):
+        f, fbs = _planes(flow, dev, torch.float32, n, "flow")
+        s, sbs = _planes(src, dev, src.dtype, n, "source")
+        sm, smbs = (None, 0) if src_mask is None else _planes(src_mask, dev, torch.bool, n, "source mask")
+        fm, fmbs = (None, 0) if flow_mask is None else _planes(flow_mask, dev, torch.bool, n, "flow mask")
+        dst = torch.empty((n, c, h, w), dtype=src.dtype, device=dev)
+        valid = torch.empty((n, h, w), dtype=torch.bool, device=dev) if want_valid else None
+        rc = lib.ofl_warp_bwd_x16(_ptr(f), fbs, float(flow_sign), _ptr(s), sbs, None, 0, _ptr(sm), smbs, _ptr(fm), fmbs, None, 0,
+                                  1.0, 1.0, _ptr(dst), _ptr(valid), None, None, None, n, c, h, w, ROUND_NONE,
+                                  _X16_DTYPES[src.dtype], _stream(dev))
+        if rc == -4:
+            return None
+        _check(rc, "ofl_warp_bwd_x16")
+    return dst, valid, None, None
+
+
+def warp_bwd_keep16(flow, src, **kw):
+    """`warp_bwd` for the TENSOR target of Flow.apply / apply_flow 't' stored in fp16 / bf16 on the device: warped from and to
+    its 16-bit planes (`_warp_bwd_x16`), dst in the source's dtype, with a grad_fn that keeps the 16-bit source when something
+    requires a gradient.  None when the call is not of that kind or the library declines the launch: the caller takes
+    `warp_bwd`, which up-converts and returns fp32."""
+    if src.dtype not in _X16_DTYPES or src.device.type != 'cuda':
+        return None
+    if flow.dtype == torch.float16:
+        flow = flow.float()                       # (the warper itself is read as fp32: exact up-conversion, utils.py:118)
+    if _wants_grad(flow, src):
+        from . import _autograd
+        return _autograd.warp(flow, src, keep16=True, **kw)
+    return _warp_bwd_x16(flow, src, **kw)
+
+
 def warp_bwd(flow, src, **kw):
     """G-family primitive; see `_warp_bwd_raw` for the arguments.  When autograd is recording and the flow, the source,
     `src_b` or the addend requires a gradient, the launch goes through `_autograd.WarpFn` (backward kernels:
-    ofl_warp_bwd_grad_f32) -- the reference's outputs are differentiable wrt flow and target (utils.py:555)."""
+    ofl_warp_bwd_grad_f32) -- the reference's outputs are differentiable wrt flow and target (utils.py:555).
+    A 16-bit `src` is up-converted here and dst is fp32 (a Flow as the target: fp16-stored flows give fp32 results); TENSOR
+    targets in fp16 / bf16 go through `warp_bwd_keep16` first."""
     if (flow.dtype is torch.float32 and flow.device.type == 'cuda'
             and not (torch.is_grad_enabled() and (flow.requires_grad or src.requires_grad))):
         res = _warp_bwd_lean(flow, src, **kw)

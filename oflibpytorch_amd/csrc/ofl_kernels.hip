@@ -25,6 +25,9 @@ int ofl_wide_launch_rows_h(const void* params, void* stream);                  /
 int ofl_wide_launch_rows_grad(const void* params, int nc, int tiles, void* stream);       // gradient wrt the flow on the row-table kernel
 int ofl_wide_launch_rows_u8(const void* params, int nc, int dst_is_u8, void* stream);         // uint8 images (bytes in; bytes or fp32 out) on the row-table kernel
 int ofl_wide_launch_chan(const void* params, int valid, int rows, void* stream);      // the channel-loop kernel (C >= 4) on 64 x 16 tiles; rows: per-row extents where they apply
+// the warp-path / shear options of ofl_set_option, for the 16-bit launcher (ofl_warp_half.hip: this file compiled with OFL_X16_TU)
+int ofl_warp_path_option(void);
+int ofl_warp_shear_option(void);
 // the gather splat's diet kernel (ofl_splat_gather.hip: this file compiled with OFL_SPLAT_TU); `params` = a GatherParams; elem: 0 fp32, 1 fp16 in / fp32 out, 2 fp16 in and out
 int ofl_splat_launch_gather_diet(const void* params, int nc, int mch, int elem, unsigned grid, void* stream, int extra_lds);   // extra_lds: bytes of dynamic LDS added to the launch (OFL_OPT_SPLAT_EXTRA_LDS: occupancy experiments)
 
@@ -217,6 +220,31 @@ __device__ __forceinline__ void st4(_Float16* p, f4 v) { *reinterpret_cast<h4u*>
 __device__ __forceinline__ void st2(_Float16* p, f2 v) { *reinterpret_cast<h2u*>(p) = (h2u){(_Float16)v[0], (_Float16)v[1]}; }
 __device__ __forceinline__ void st1(float* p, float v) { *p = v; }
 __device__ __forceinline__ void st1(_Float16* p, float v) { *p = (_Float16)v; }
+// feature tensors stored in bfloat16 (ofl_warp_bwd_x16, ofl_warp_half.hip): the same set once more.  A bf16 value is the upper half of
+// the fp32 with the same value, so the up-conversion is a shift; a store rounds to nearest even, NaN to a quiet NaN (bf16_rn: the
+// compiler's float -> __bf16 conversion, v_cvt_pk_bf16_f32 on gfx950) -- what `Tensor.to(torch.bfloat16)` gives.  The accesses are
+// declared at the ELEMENT's alignment (2 bytes): a row starts on an odd element when W is odd, a plane when H * W is odd, and gfx950
+// serves a wider access at any byte address (as the 16-byte accesses at 4-byte alignment above).
+struct bf16_t { uint16_t bits; };
+typedef uint16_t us4u __attribute__((ext_vector_type(4), aligned(2)));
+typedef uint16_t us2u __attribute__((ext_vector_type(2), aligned(2)));
+__device__ __forceinline__ float bf16_up(uint32_t b) { return __builtin_bit_cast(float, b << 16); }
+__device__ __forceinline__ uint16_t bf16_rn(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
+__device__ __forceinline__ f4 ld4(const bf16_t* p) { const us4u v = *reinterpret_cast<const us4u*>(p); return (f4){bf16_up(v[0]), bf16_up(v[1]), bf16_up(v[2]), bf16_up(v[3])}; }
+__device__ __forceinline__ f2 ld2(const bf16_t* p) { const us2u v = *reinterpret_cast<const us2u*>(p); return (f2){bf16_up(v[0]), bf16_up(v[1])}; }
+__device__ __forceinline__ float ld1(const bf16_t* p) { return bf16_up(p->bits); }
+__device__ __forceinline__ void st4(bf16_t* p, f4 v) { *reinterpret_cast<us4u*>(p) = (us4u){bf16_rn(v[0]), bf16_rn(v[1]), bf16_rn(v[2]), bf16_rn(v[3])}; }
+__device__ __forceinline__ void st2(bf16_t* p, f2 v) { *reinterpret_cast<us2u*>(p) = (us2u){bf16_rn(v[0]), bf16_rn(v[1])}; }
+__device__ __forceinline__ void st1(bf16_t* p, float v) { p->bits = bf16_rn(v); }
+// ... and in fp16: the _Float16 set above under a name of its own, so that the instantiations on 16-bit TENSORS report a storage type
+// that every demangler prints (ofl_last_kernel_name: `half_t` / `bf16_t`)
+struct half_t { _Float16 v; };
+__device__ __forceinline__ f4 ld4(const half_t* p) { return ld4(reinterpret_cast<const _Float16*>(p)); }
+__device__ __forceinline__ f2 ld2(const half_t* p) { return ld2(reinterpret_cast<const _Float16*>(p)); }
+__device__ __forceinline__ float ld1(const half_t* p) { return (float)p->v; }
+__device__ __forceinline__ void st4(half_t* p, f4 v) { st4(reinterpret_cast<_Float16*>(p), v); }
+__device__ __forceinline__ void st2(half_t* p, f2 v) { st2(reinterpret_cast<_Float16*>(p), v); }
+__device__ __forceinline__ void st1(half_t* p, float v) { p->v = (_Float16)v; }
 // write-once outputs of the staged warp: non-temporal, so that they stream past the L2 lines the halos live in (+0.5 .. 1 %);
 // the gather splat's 16-byte output stores use it too (+1 % on smooth flows).  (Also measured, within +-1 %:
 // non-temporal flow-mask loads, non-temporal loads in the splat's bin kernel.)
@@ -1381,8 +1409,8 @@ __device__ __forceinline__ void lds_taps(const WP& p, const LdsCoords& T, const 
 // arithmetic of lds_gather_impl -- so that nothing of it is kept in registers across the channel loop.  Cold (a wave with no such
 // lane skips it), and a real call for the same reason as above.
 struct Out4 { f4 v[4]; };
-template <int NCH, bool MASK3>
-__device__ __attribute__((noinline)) Out4 chan_pixels_from_global(WarpParamsK* pp, const float* sb, uint32_t pix, uint32_t below, Out4 cur,
+template <int NCH, bool MASK3, typename TS = float>
+__device__ __attribute__((noinline)) Out4 chan_pixels_from_global(WarpParamsK* pp, const TS* sb, uint32_t pix, uint32_t below, Out4 cur,
                                                                   int tx, int ty, int n, int row) {
 #define p (*pp)
     const int w = p.w, h = p.h;
@@ -1396,7 +1424,7 @@ __device__ __attribute__((noinline)) Out4 chan_pixels_from_global(WarpParamsK* p
     LdsBox Bx = {};
     Bx.fits = false; Bx.interior = false; Bx.clipped = false;
     f4 got[4];
-    lds_gather_impl<NCH, MASK3, false>(p, hw, sb, MASK3 ? sm : nullptr, Tc, Bx, nullptr, got);
+    lds_gather_impl<NCH, MASK3, false, false, TS>(p, hw, sb, MASK3 ? sm : nullptr, Tc, Bx, nullptr, got);
 #pragma unroll
     for (int k = 0; k < 4; ++k) if ((below >> k) & 1u) cur.v[k] = got[k];
     return cur;
@@ -1441,7 +1469,9 @@ __device__ __forceinline__ void rows_taps(const WP& p, const LdsCoords& T, const
     }
 }
 
-template <bool VALID, bool LEAN = false, int SUBS = 1, bool ROWS = false>
+// (TS / TD: planes stored in fp16 / bf16 -- ofl_warp_bwd_x16 -- are up-converted at the staging load and rounded once at the store; the
+// staged box and everything between is fp32, as for the other kernels' 16-bit instantiations.)
+template <bool VALID, bool LEAN = false, int SUBS = 1, bool ROWS = false, typename TS = float, typename TD = float>
 __global__ __launch_bounds__(kLdsNT * SUBS, 3) void warp_bwd_lds_chan_kernel(const WarpParams p_by_value) {
     static_assert(!ROWS || (LEAN && SUBS == 1), "ROWS: lean launches, one tile per block");
     typedef typename std::conditional<LEAN, WarpParamsLeanK, WarpParamsK>::type WPK;       // (LEAN: see WarpParamsLean)
@@ -1461,7 +1491,7 @@ __global__ __launch_bounds__(kLdsNT * SUBS, 3) void warp_bwd_lds_chan_kernel(con
     const int w = p.w, h = p.h, C = p.c;
     const uint32_t hw = (uint32_t)(h * w);
     const float* __restrict__ fu = p.flow + n * p.flow_bs;
-    const float* __restrict__ sb0 = p.src + n * p.src_bs;
+    const TS* __restrict__ sb0 = reinterpret_cast<const TS*>(p.src) + n * p.src_bs;
     const uint8_t* __restrict__ sm = p.src_mask ? p.src_mask + n * p.src_mask_bs : nullptr;
     const uint8_t* __restrict__ fm = p.flow_mask ? p.flow_mask + n * p.flow_mask_bs : nullptr;
     const int x4 = tx * (kLdsTWQ * 4) + lx * 4, xq = min(x4, w - 4);
@@ -1568,7 +1598,7 @@ __global__ __launch_bounds__(kLdsNT * SUBS, 3) void warp_bwd_lds_chan_kernel(con
 
     f4 q[kLdsIters][4];                                      // the staged group: [round][plane] = 4 pixels of one plane
     // staging loads of the 4 planes at `sb` (mask3: the fourth plane is the target mask's bytes, as 0 / 1 floats)
-    auto issue = [&](const float* __restrict__ sb, bool mask3) {
+    auto issue = [&](const TS* __restrict__ sb, bool mask3) {
 #pragma unroll
         for (int it = 0; it < kLdsIters; ++it) {
             if (it == 0 || it < rounds) {
@@ -1608,7 +1638,7 @@ __global__ __launch_bounds__(kLdsNT * SUBS, 3) void warp_bwd_lds_chan_kernel(con
             outv[k] = r;
         }
     };
-    float* __restrict__ db = p.dst + (int64_t)n * p.dst_bs;
+    TD* __restrict__ db = reinterpret_cast<TD*>(p.dst) + (int64_t)n * p.dst_bs;
     auto store = [&](const f4 (&outv)[4], int first, int planes) {   // planes `first` .. of dst (unconditional: see lds_store)
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -1630,7 +1660,7 @@ __global__ __launch_bounds__(kLdsNT * SUBS, 3) void warp_bwd_lds_chan_kernel(con
         gather(outv);
         if (__builtin_expect(any_below, 0)) {
             if (below != 0u) {
-                const Out4 fixed = chan_pixels_from_global<3, true>(reinterpret_cast<WarpParamsK*>(pp), sb0, pix, below, Out4{{outv[0], outv[1], outv[2], outv[3]}}, tx, ty, n, ly);
+                const Out4 fixed = chan_pixels_from_global<3, true, TS>(reinterpret_cast<WarpParamsK*>(pp), sb0, pix, below, Out4{{outv[0], outv[1], outv[2], outv[3]}}, tx, ty, n, ly);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) outv[k] = fixed.v[k];
             }
@@ -1658,7 +1688,7 @@ __global__ __launch_bounds__(kLdsNT * SUBS, 3) void warp_bwd_lds_chan_kernel(con
         gather(outv);
         if (__builtin_expect(any_below, 0)) {
             if (below != 0u) {
-                const Out4 fixed = chan_pixels_from_global<4, false>(reinterpret_cast<WarpParamsK*>(pp), sb0 + (int64_t)mine * hw, pix, below, Out4{{outv[0], outv[1], outv[2], outv[3]}}, tx, ty, n, ly);
+                const Out4 fixed = chan_pixels_from_global<4, false, TS>(reinterpret_cast<WarpParamsK*>(pp), sb0 + (int64_t)mine * hw, pix, below, Out4{{outv[0], outv[1], outv[2], outv[3]}}, tx, ty, n, ly);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) outv[k] = fixed.v[k];
             }
@@ -3916,6 +3946,100 @@ int ofl_wide_launch_chan(const void* params, int valid, int rows, void* stream) 
     else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false>), dim3(g1), dim3(kLdsNT), kLdsBytes, (hipStream_t)stream, q);
     return (int)hipGetLastError();
 }
+#elif defined(OFL_X16_TU)
+// This translation unit (ofl_warp_half.hip) provides ofl_warp_bwd_x16: the plain backward warp of planes STORED in fp16 / bf16 (feature
+// tensors under autocast), on the TS = TD = half_t / bf16_t instantiations of the staged kernels above, 64 x 16 tiles.  The launch
+// decisions follow launch_warp_lds / warp_bwd_impl (thresholds in THEIR 32-wide geometry, so that a 16-bit call changes kernel where
+// the fp32 call does), with fewer branches: lean launches (W % 4 == 0) of up to 3 planes run the row-table kernel with 1 / 2 / 4 tiles
+// per block, the others the sheared rectangle's one-tile / pair / four-tile kernels; from 4 planes on (7 with the valid area) the
+// channel loop.  What a kernel here cannot take is declined (OFL_E_UNSUPPORTED) and the caller converts and calls ofl_warp_bwd_f32.
+constexpr unsigned kX16ColumnMin = 6912;       // (kColumnMinGroups of launch_warp_lds)
+inline unsigned x16_tiles(const WarpParams& p, int tw, int th) {   // blocks of a launch on tw x th tiles (warp_geometry's count)
+    const int64_t t = (int64_t)((p.w + tw - 1) / tw) * ((p.h + th - 1) / th) * p.n;
+    return (unsigned)(((t + kXcds - 1) / kXcds) * kXcds);
+}
+template <typename TX, int NC, bool V>
+int x16_launch_group(const WarpParams& p, hipStream_t st) {
+    WarpParams q = p;
+    const unsigned g1 = x16_tiles(p, 32, 16), g4 = x16_tiles(p, 32, 64);
+    constexpr int TT = kLdsT > 2 ? kLdsT : 3, RT = OFL_ROWS_T;
+    if (warp_is_lean(q)) {
+        if (g4 >= OFL_ROWS_T4_MIN) OFL_KLAUNCH((warp_bwd_rows_kernel<RT, NC, V, 0, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH)), dim3(kLdsNT), kRowsLdsBytes, st, q);
+        else if (g1 < OFL_ROWS_T1_MAX) OFL_KLAUNCH((warp_bwd_rows_kernel<1, NC, V, 0, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, kLdsTH)), dim3(kLdsNT), kRowsLdsBytes, st, q);
+        else OFL_KLAUNCH((warp_bwd_rows_kernel<2, NC, V, 0, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, 2 * kLdsTH)), dim3(kLdsNT), kRowsLdsBytes, st, q);
+        return (int)hipGetLastError();
+    }
+    // a width that is no multiple of 4 (or no shear: a frame too wide for 16-bit sheared rows): the sheared rectangle / plain box
+    if (g1 < kX16ColumnMin) OFL_KLAUNCH((warp_bwd_lds_column_kernel<1, NC, V, false, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, kLdsTH)), dim3(kLdsNT), kLdsBytes, st, q);
+    else if (g4 >= kX16ColumnMin) OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, NC, V, false, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, TT * kLdsTH)), dim3(kLdsNT), kLdsBytes, st, q);
+    else OFL_KLAUNCH((warp_bwd_lds_kernel<NC, V, false, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, 2 * kLdsTH)), dim3(kLdsNT), kLdsBytes, st, q);
+    return (int)hipGetLastError();
+}
+template <typename TX>
+int x16_launch(WarpParams p, const void* src, void* dst, hipStream_t st) {
+    const int32_t c = p.c;
+    const int64_t hw = (int64_t)p.h * p.w;
+    p.src = reinterpret_cast<const float*>(src); p.dst = reinterpret_cast<float*>(dst);      // (the kernels re-read these as TX pointers)
+    // more than 3 planes: ONE launch that walks them inside the block (see warp_bwd_impl: 7 with the valid area; per-row extents from
+    // two channel groups on)
+    if (c >= (p.valid ? 7 : 4) && warp_is_lean(p)) {
+        WarpParams q = p;
+        const unsigned g1 = warp_geometry(q, kLdsTWQ * 4, kLdsTH);
+        if (c >= 7) {
+            if (q.valid) OFL_KLAUNCH((warp_bwd_lds_chan_kernel<true, true, 1, true, TX, TX>), dim3(g1), dim3(kLdsNT), kRowsLdsBytes, st, q);
+            else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, true, 1, true, TX, TX>), dim3(g1), dim3(kLdsNT), kRowsLdsBytes, st, q);
+        } else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, true, 1, false, TX, TX>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q);
+        return (int)hipGetLastError();
+    }
+    // otherwise groups of 3; the valid mask comes out of the first group
+    for (int32_t c0 = 0; c0 < c; c0 += 3) {
+        const int32_t nc = (c - c0) < 3 ? (c - c0) : 3;
+        WarpParams q = p;
+        q.c = nc;
+        q.src = reinterpret_cast<const float*>(static_cast<const TX*>(src) + c0 * hw);
+        q.dst = reinterpret_cast<float*>(static_cast<TX*>(dst) + c0 * hw);
+        if (c0 > 0) { q.valid = nullptr; q.src_mask = nullptr; }
+        int rc;
+        if (q.valid) rc = nc == 1 ? x16_launch_group<TX, 1, true>(q, st) : nc == 2 ? x16_launch_group<TX, 2, true>(q, st) : x16_launch_group<TX, 3, true>(q, st);
+        else rc = nc == 1 ? x16_launch_group<TX, 1, false>(q, st) : nc == 2 ? x16_launch_group<TX, 2, false>(q, st) : x16_launch_group<TX, 3, false>(q, st);
+        if (rc) return rc;
+    }
+    return OFL_OK;
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("default"))) int ofl_warp_bwd_x16(
+    const float* flow, int64_t flow_bs, float flow_sign, const void* src, int64_t src_bs,
+    const void* src_b, int64_t src_b_bs, const uint8_t* src_mask, int64_t src_mask_bs, const uint8_t* flow_mask, int64_t flow_mask_bs,
+    const void* addend, int64_t addend_bs, float a_sign, float g_sign, void* dst, uint8_t* valid,
+    int32_t* flow_flags, int32_t* src_flags, int32_t* dst_flags, int32_t n, int32_t c, int32_t h, int32_t w,
+    int32_t round_mode, int32_t dtype, void* stream) {
+    (void)src_b_bs; (void)addend_bs; (void)a_sign; (void)g_sign;
+    if (!flow || !src || !dst) return OFL_E_NULL;
+    int rc = check_dims(n, c, h, w, false);
+    if (rc) return rc;
+    if (dtype != OFL_X16_HALF && dtype != OFL_X16_BFLOAT) return OFL_E_ARG;
+    if (round_mode < 0 || round_mode > 2) return OFL_E_ARG;
+    if (!(flow_sign == 1.0f || flow_sign == -1.0f)) return OFL_E_ARG;
+    if ((int64_t)((w + 31) / 32) * ((h + 15) / 16) * n >= (1ll << 31)) return OFL_E_SHAPE;
+    // the plain warp only: no addend, no subtracted source, no flag words, no rounding (and no flow window: ofl_warp_bwd_win_f32)
+    if (src_b || addend || flow_flags || src_flags || dst_flags || round_mode != OFL_ROUND_NONE) return OFL_E_UNSUPPORTED;
+    // staged kernels only (the conditions of warp_bwd_impl), on the automatic path (OFL_OPT_WARP_PATH picks among the fp32 kernels)
+    if (!(ofl_warp_path_option() == 0 && w >= 4 && h >= 2 && w < 32760 && h < 32760 && (int64_t)h * w < (1ll << 24))) return OFL_E_UNSUPPORTED;
+    WarpParams p = {};
+    p.flow = flow; p.flow_bs = flow_bs; p.src_bs = src_bs;
+    p.src_mask = src_mask; p.src_mask_bs = src_mask_bs; p.flow_mask = flow_mask; p.flow_mask_bs = flow_mask_bs;
+    p.valid = valid;
+    p.n = n; p.c = c; p.h = h; p.w = w;
+    p.flow_sign = flow_sign; p.a_sign = 1.0f; p.g_sign = 1.0f; p.round_mode = OFL_ROUND_NONE;
+    p.wm1 = (float)(w - 1); p.hm1 = (float)(h - 1);
+    p.half_wm1 = p.wm1 / 2.0f; p.half_hm1 = p.hm1 / 2.0f;
+    p.rcp_wm1 = 1.0f / p.wm1; p.rcp_hm1 = 1.0f / p.hm1;
+    p.lds_bytes = kLdsBytes;
+    p.shear = (ofl_warp_shear_option() && (int64_t)h + 4 * (int64_t)w + 8 < 32760) ? 1 : 0;
+    p.dst_bs = (int64_t)c * h * w;
+    return dtype == OFL_X16_HALF ? x16_launch<half_t>(p, src, dst, (hipStream_t)stream) : x16_launch<bf16_t>(p, src, dst, (hipStream_t)stream);
+}
 #else
 int g_warp_path = 0;   // ofl_set_option(OFL_OPT_WARP_PATH, .): 0 auto, 1 generic direct-gather kernel only, 2 (= auto), 3 / 4 staged with two tiles / one tile per block whatever the launch size (tests), 5 = auto but more than 3 channels as separate launches of 3 (tests: the channel-loop kernel against them), 6 = auto but the sheared rectangle instead of per-row extents (tests, A/B), 7 = auto but plain lean launches on four-tile row-table columns whatever the size (tests)
 int g_warp_shear = 1;   // ofl_set_option(OFL_OPT_WARP_SHEAR, .)
@@ -4181,6 +4305,8 @@ extern "C" {
 
 }  // extern "C"
 const void* g_ofl_last_kernel = nullptr;
+int ofl_warp_path_option(void) { return g_warp_path; }
+int ofl_warp_shear_option(void) { return g_warp_shear; }
 extern "C" {
 __attribute__((visibility("default"))) const char* ofl_last_kernel_name(void) {
     return g_ofl_last_kernel ? hipKernelNameRefByPtr(g_ofl_last_kernel, nullptr) : "";

@@ -686,7 +686,7 @@ class Flow(object):
         if padding is None:
             if tuple(target.shape[-2:]) != self.shape[-2:]:
                 raise ValueError("Error applying flow: Flow and target have to have the same shape")
-            warped, valid, dflags = self._warp(t, tmask, need_valid, consider_mask, rm)
+            warped, valid, dflags = self._warp(t, tmask, need_valid, consider_mask, rm, keep16=not return_flow)
         else:
             warped, valid, dflags = self._warp_padded(t, tmask, need_valid, consider_mask, rm, padding)
 
@@ -756,7 +756,8 @@ class Flow(object):
         return flow._warp(t, tmask, need_valid, consider_mask, round_mode)
 
     def _warp(self, t: torch.Tensor, tmask, need_valid: bool, consider_mask: bool, round_mode: int = 0,
-              flow_sign: float = 1.0, data_sign: float = 1.0, t_minus: torch.Tensor = None, mask_chan_b: torch.Tensor = None):
+              flow_sign: float = 1.0, data_sign: float = 1.0, t_minus: torch.Tensor = None, mask_chan_b: torch.Tensor = None,
+              keep16: bool = False):
         """Core of `apply`: t [Nt,C,H,W] any dtype, tmask [Nt,H,W] bool or None (all True).
         Returns (warped fp32 [N,C,H,W], valid bool [N,H,W] | None) on self.device.
         `flow_sign` / `data_sign` = -1 (forward flows only) restate `(-self)` as the warper / `-t` as the target inside the
@@ -764,7 +765,9 @@ class Flow(object):
         no negated copy and no second flag reduction.  `t_minus` (past the early exit only): the target is t - t_minus,
         subtracted inside the kernel (modes 1 't' / 2 's': target `flow - self`; `tmask` / the two channel masks carry
         m_flow & m_self).  `mask_chan_b` ('s' only; the padded batch-1-target case of `_warp_padded`): the batch-1 flow mask
-        that goes into the mask channel instead of this flow's own, and keeps an all-zero flow's result at batch 1."""
+        that goes into the mask channel instead of this flow's own, and keeps an all-zero flow's result at batch 1.
+        `keep16` ('t' only; a TENSOR target of `apply`): fp16 / bf16 data on the device is warped from and to its 16-bit planes
+        and `warped` comes back in that dtype (`_native.warp_bwd_keep16`)."""
         mesh = self._ref == 's' and _mesh_mode("Flow.apply(ref='s')")
         batch_flags = self._batch_flags()                                             # (one look at the cached word for both tests)
         if batch_flags & _native.FLAG_NONFINITE:                                      # utils.py:98
@@ -796,10 +799,16 @@ class Flow(object):
         if mesh:
             warped, valid = self._warp_mesh(t, tmask, need_valid, consider_mask, round_mode, flow_sign, data_sign, t_minus, mask_chan_b)
         elif self._ref == 't':
-            warped, valid, _, _ = _native.warp_bwd(self._fv, t, src_mask=tmask,
-                                                   flow_mask=self._mask if need_valid else None,
-                                                   want_valid=need_valid, round_mode=round_mode, src_b=t_minus,
-                                                   out_uint8=not get_pure_pytorch())   # (:943-949: only then is it cast back)
+            res = None
+            if keep16 and t_minus is None and t.dtype in _native._X16_DTYPES:
+                res = _native.warp_bwd_keep16(self._fv, t, src_mask=tmask, flow_mask=self._mask if need_valid else None,
+                                              want_valid=need_valid, round_mode=round_mode)
+            if res is None:
+                res = _native.warp_bwd(self._fv, t, src_mask=tmask,
+                                       flow_mask=self._mask if need_valid else None,
+                                       want_valid=need_valid, round_mode=round_mode, src_b=t_minus,
+                                       out_uint8=not get_pure_pytorch())   # (:943-949: only then is it cast back)
+            warped, valid = res[0], res[1]
         else:
             # a warped FLOW (2 channels, with its valid mask) brings its flag word along: the splat produces it as a
             # by-product, so that using the result as a warper needs no validation pass of its own
