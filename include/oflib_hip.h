@@ -253,7 +253,8 @@ int ofl_splat_tile_geometry(int32_t* tile_w, int32_t* tile_h, int32_t* list_capa
 /* resources of the gather kernel the given kind of call runs on (round 6: the evidence behind "three blocks per CU"), as the HIP
  * runtime reports them for the loaded code object: info4[0] = 512-thread blocks resident per CU (with `extra_lds` bytes of dynamic
  * LDS added, see OFL_OPT_SPLAT_EXTRA_LDS), [1] = static LDS bytes per block, [2] = VGPRs, [3] = scratch bytes per thread.
- * channels 1..3; elem 0 = fp32, 1 = fp16 in / fp32 out, 2 = fp16 in and out (2 channels); lean: the common-case instantiation
+ * channels 1..3; elem 0 = fp32, 1 = fp16 in / fp32 out, 2 = fp16 in and out (2 channels), 3 / 4 = an fp32 flow with fp16 / bf16 data
+ * and dst (ofl_splat_sum_x16; no mask channel); lean: the common-case instantiation
  * (a flow, no window, W % 4 == 0, no rounding; 2 and 3 channels).  Needs a HIP device. */
 int ofl_splat_gather_info(int32_t channels, int32_t with_mask_chan, int32_t elem, int32_t lean, int32_t extra_lds, int32_t* info4);
 int ofl_splat_tiled_f32(const float* flow, int64_t flow_bs, float flow_sign,
@@ -427,6 +428,35 @@ int ofl_warp_bwd_x16(const float* flow, int64_t flow_bs, float flow_sign,
                      int32_t* flow_flags, int32_t* src_flags, int32_t* dst_flags,
                      int32_t n, int32_t c, int32_t h, int32_t w,
                      int32_t round_mode, int32_t dtype, void* stream);
+
+/*
+ * The BACKWARD pass of ofl_warp_bwd_x16, from and to the 16-bit planes: no fp32 copy of the source, of the upstream gradient or of
+ * the source gradient.  Both are gathers without float atomics and compute what their fp32 siblings compute on the up-converted
+ * inputs, bit for bit: the 16-bit values are up-converted at the load (exact), the fp32 arithmetic and its order are the siblings',
+ * and a 16-bit output is rounded ONCE, to nearest even, at the store.  `dtype` as above (OFL_E_ARG for another); 16-bit planes at
+ * 2-byte alignment, any W; negative batch strides are OFL_E_ARG.
+ *
+ *   ofl_warp_bwd_grad_x16   the gradient with respect to the FLOW: the arguments of ofl_warp_bwd_grad_f32 without grad_src /
+ *                           grad_src_bs (that gradient is ofl_splat_sum_x16), src [*,C,H,W] and grad_out [N,C,H,W] (contiguous)
+ *                           planes of `dtype`; grad_flow fp32 [N,2,H,W], written, not accumulated.  Up to 3 planes run the GRAD
+ *                           instantiations of the staged kernels on `half_t` / `bf16_t`; more planes one pixel per lane, as the
+ *                           fp32 entry point does (the sums chain over all planes).  A frame the staged kernels do not take
+ *                           (W < 4, H < 2, H*W >= 2^24), or a call off the automatic OFL_OPT_WARP_PATH, returns
+ *                           OFL_E_UNSUPPORTED and launches nothing: convert and call ofl_warp_bwd_grad_f32.
+ *   ofl_splat_sum_x16       the gradient with respect to the SOURCE: ofl_splat_sum_f32 (raw weighted sums) with an fp32 flow,
+ *                           `data` (the upstream gradient) and `dst` planes of `dtype`.  The gather kernel up-converts the data
+ *                           at its record loads and sums in fp32 in its own order; the band launch and the fallback accumulator
+ *                           stay fp32; only the store that produces dst converts.  Workspace, fallback accumulator, limits and
+ *                           OFL_E_UNSUPPORTED cases of ofl_splat_sum_f32.
+ */
+int ofl_warp_bwd_grad_x16(const float* flow, int64_t flow_bs, float flow_sign,
+                          const void* src, int64_t src_bs,
+                          const void* grad_out, float g_scale, float* grad_flow,
+                          int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype, void* stream);
+int ofl_splat_sum_x16(const float* flow, int64_t flow_bs, float flow_sign,
+                      const void* data, int64_t data_bs, float data_sign, void* dst,
+                      int32_t* workspace, int64_t workspace_ints, float* accum_fallback,
+                      int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------------

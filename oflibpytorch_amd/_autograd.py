@@ -54,7 +54,15 @@ class WarpFn(torch.autograd.Function):
         flow, src, src_b = ctx.saved_tensors
         flow_sign, a_sign, g_sign = ctx.signs
         need_flow, need_src, need_add, need_b = ctx.needs_input_grad[:4]
+        dense = g.is_contiguous()                         # (a strided upstream gradient -- channels-last -- keeps the present route)
         g = g.contiguous()
+        if (dense and src.dtype in _native._X16_DTYPES and src.device.type == 'cuda' and g.dtype == src.dtype and src_b is None
+                and ctx.addend_meta is None and src.shape[0] == g.shape[0] and (need_flow or need_src)):
+            # a 16-bit source that took the native forward: both gradients from the 16-bit planes (no fp32 copy of the source, of g or of
+            # the source gradient); a source broadcast over the batch sums its gradient in fp32 below, as does a launch the library declines
+            res = _native.warp_bwd_grad_x16(flow, src, g, flow_sign=flow_sign, g_scale=g_sign, want_src=bool(need_src), want_flow=bool(need_flow))
+            if res is not None:
+                return (_reduce_to(res[1], flow) if need_flow else None), (res[0] if need_src else None), None, None, None
         gathered = src.detach().float()
         if src_b is not None:
             gathered = gathered.to(g.device) - src_b.detach().float().to(g.device)

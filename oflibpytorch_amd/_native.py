@@ -31,7 +31,7 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_matrix_workspace_bytes", "ofl_matrix_fit_f64",
             "ofl_arrows_workspace_ints", "ofl_arrows_scale_f32", "ofl_arrows_plan", "ofl_arrows_u8",
             "ofl_mesh_workspace_ints", "ofl_mesh_plan", "ofl_mesh_apply", "ofl_mesh_points",
-            "ofl_warp_bwd_x16")
+            "ofl_warp_bwd_x16", "ofl_warp_bwd_grad_x16", "ofl_splat_sum_x16")
 _lib = None
 
 
@@ -119,6 +119,8 @@ def load_library(path: str = None):
     lib.ofl_mesh_points.argtypes = [p, i64, f32, p, i64, p, i64, p, p, i64, p, p, i32, i32, i32, i32, p]
     lib.ofl_warp_bwd_x16.argtypes = [p, i64, f32, p, i64, p, i64, p, i64, p, i64, p, i64, f32, f32, p, p, p, p, p,
                                      i32, i32, i32, i32, i32, i32, p]
+    lib.ofl_warp_bwd_grad_x16.argtypes = [p, i64, f32, p, i64, p, f32, p, i32, i32, i32, i32, i32, p]
+    lib.ofl_splat_sum_x16.argtypes = [p, i64, f32, p, i64, f32, p, p, i64, p, i32, i32, i32, i32, i32, p]
     for name in _SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     lib.ofl_arrows_workspace_ints.restype = ctypes.c_int64
@@ -840,6 +842,47 @@ def warp_bwd_grad(flow, src, grad_out, *, flow_sign=1.0, g_scale=1.0, want_src=T
                                              _ptr(gs) if atomics else None, 0 if ns == 1 else c * h * w, _ptr(gf), n, c, h, w,
                                              _stream(dev)),
                    "ofl_warp_bwd_grad_f32")
+    return gs, gf
+
+
+def warp_bwd_grad_x16(flow, src16, grad_out16, *, flow_sign=1.0, g_scale=1.0, want_src=True, want_flow=True):
+    """Backward of G for a 16-bit source on the device, from its 16-bit planes (ofl_splat_sum_x16 / ofl_warp_bwd_grad_x16): no fp32
+    copy of the source, of the upstream gradient or of the source gradient.  flow [N|1,2,H,W], src16 [N,C,H,W] and grad_out16
+    [N,C,H,W] contiguous, of one 16-bit dtype -> (grad_src in src16.dtype | None, grad_flow fp32 [N,2,H,W] | None) -- bit-identical
+    to `warp_bwd_grad` on the up-converted tensors followed by `.to(dtype)`.  None when the call is not of that kind (another dtype or
+    device, a source broadcast over the batch: its gradient is summed over the batch in fp32) or the library declines a launch;
+    nothing has been computed then and the caller takes `warp_bwd_grad`."""
+    dt = src16.dtype
+    if (dt not in _X16_DTYPES or grad_out16.dtype != dt or src16.device.type != 'cuda' or grad_out16.device != src16.device
+            or src16.dim() != 4 or src16.shape != grad_out16.shape or not (want_src or want_flow)):
+        return None
+    n, c, h, w = grad_out16.shape
+    if w < 4 or h < 2 or h * w >= (1 << 24) or h >= 32760 or w >= 32760 or flow.shape[0] not in (1, n):
+        return None                         # frames the staged warp kernels / the gather splat do not take
+    lib, dev = load_library(), src16.device
+    with _on(dev):
+        f, fbs = _planes(flow.detach(), dev, torch.float32, n, "flow")
+        s, g = src16.detach().contiguous(), grad_out16.detach().contiguous()
+        gs = gf = None
+        if want_flow:
+            gf = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+            rc = lib.ofl_warp_bwd_grad_x16(_ptr(f), fbs, float(flow_sign), _ptr(s), c * h * w, _ptr(g), float(g_scale), _ptr(gf),
+                                           n, c, h, w, _X16_DTYPES[dt], _stream(dev))
+            if rc == -4:
+                return None
+            _check(rc, "ofl_warp_bwd_grad_x16")
+        if want_src:
+            ws = torch.empty(int(lib.ofl_splat_tiled_workspace_ints(n, h, w)), dtype=torch.int32, device=dev)
+            accum = _fallback_accum(lib, n, c, 0, h, w, dev)
+            gs = torch.empty((n, c, h, w), dtype=dt, device=dev)
+            rc = lib.ofl_splat_sum_x16(_ptr(f), fbs, -float(flow_sign), _ptr(g), c * h * w, float(g_scale), _ptr(gs), _ptr(ws), ws.numel(),
+                                       _ptr(accum), n, c, h, w, _X16_DTYPES[dt], _stream(dev))
+            if rc in (-4, -2):
+                return None
+            _check(rc, "ofl_splat_sum_x16")
+            if collect_splat_stats:
+                global _last_splat_stats
+                _last_splat_stats = ws[:8].clone()
     return gs, gf
 
 

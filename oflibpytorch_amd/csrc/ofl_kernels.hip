@@ -28,7 +28,7 @@ int ofl_wide_launch_chan(const void* params, int valid, int rows, void* stream);
 // the warp-path / shear options of ofl_set_option, for the 16-bit launcher (ofl_warp_half.hip: this file compiled with OFL_X16_TU)
 int ofl_warp_path_option(void);
 int ofl_warp_shear_option(void);
-// the gather splat's diet kernel (ofl_splat_gather.hip: this file compiled with OFL_SPLAT_TU); `params` = a GatherParams; elem: 0 fp32, 1 fp16 in / fp32 out, 2 fp16 in and out
+// the gather splat's diet kernel (ofl_splat_gather.hip: this file compiled with OFL_SPLAT_TU); `params` = a GatherParams; elem: 0 fp32, 1 fp16 in / fp32 out, 2 fp16 in and out, 3 / 4 fp32 flow with fp16 / bf16 data and dst (no mask channel)
 int ofl_splat_launch_gather_diet(const void* params, int nc, int mch, int elem, unsigned grid, void* stream, int extra_lds);   // extra_lds: bytes of dynamic LDS added to the launch (OFL_OPT_SPLAT_EXTRA_LDS: occupancy experiments)
 
 // the kernel the library launched LAST, in any of its translation units (ofl_last_kernel_name: bench.py reports the instantiation
@@ -245,6 +245,12 @@ __device__ __forceinline__ float ld1(const half_t* p) { return (float)p->v; }
 __device__ __forceinline__ void st4(half_t* p, f4 v) { st4(reinterpret_cast<_Float16*>(p), v); }
 __device__ __forceinline__ void st2(half_t* p, f2 v) { st2(reinterpret_cast<_Float16*>(p), v); }
 __device__ __forceinline__ void st1(half_t* p, float v) { p->v = (_Float16)v; }
+// Element types of a splat's operands.  `TF` names the type the FLOW and the DATA planes are stored in (float, or _Float16 for flows stored
+// in fp16: the flow is its own data there).  SpMixed<TD> in its place keeps the flow fp32 and gives the data planes a type of their own:
+// the gradient of a 16-bit warp with respect to its source (ofl_splat_sum_x16) splats a 16-bit upstream gradient along an fp32 flow.
+template <typename TD> struct SpMixed {};
+template <typename TF> struct sp_el { typedef TF flow; typedef TF data; };
+template <typename TD> struct sp_el<SpMixed<TD>> { typedef float flow; typedef TD data; };
 // write-once outputs of the staged warp: non-temporal, so that they stream past the L2 lines the halos live in (+0.5 .. 1 %);
 // the gather splat's 16-byte output stores use it too (+1 % on smooth flows).  (Also measured, within +-1 %:
 // non-temporal flow-mask loads, non-temporal loads in the splat's bin kernel.)
@@ -745,12 +751,13 @@ __device__ __forceinline__ void lds_gather(const WP& p, uint32_t hw,
 }
 
 // the fused addend of a tile (mode 3), loaded ahead of younger loads and stores: the wait for it must not cover them
-template <int NC, typename WP = WarpParams>
+// (TA: the type its planes are stored in -- the upstream gradient of a 16-bit warp, ofl_warp_bwd_grad_x16, is 16-bit; exact up-conversion)
+template <int NC, typename TA = float, typename WP = WarpParams>
 __device__ __forceinline__ void lds_load_addend(const WP& p, int tx, int ty, int n, uint32_t hw, f4 (&a)[NC]) {
     const int tid = threadIdx.x, lx = tid % kLdsTWQ, ly = tid / kLdsTWQ;
     const uint32_t pix = (uint32_t)(min(ty * kLdsTH + ly, p.h - 1) * p.w + min(tx * (kLdsTWQ * 4) + lx * 4, p.w - 4));
 #pragma unroll
-    for (int c = 0; c < NC; ++c) a[c] = ld4(p.addend + n * p.addend_bs + c * hw + pix);
+    for (int c = 0; c < NC; ++c) a[c] = ld4(reinterpret_cast<const TA*>(p.addend) + n * p.addend_bs + c * hw + pix);
 }
 
 // step 4b: valid mask, epilogue (a_sign * addend + g_sign * G, rounding), 16-byte stores
@@ -962,7 +969,7 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_lds_column_kernel(const Wa
         if (k + 1 < T) { if (more) lds_coords_box_b<kClip>(p, sq[k + 1], wn, Bx[k + 1], red[(k + 1) & 1]); }
         f4 outv[4], ad[NC];
         if (EARLY) { if (reuse) { ad[0] = uu[k]; ad[NC - 1] = vv[k]; } else lds_load_addend<NC>(p, tx, tyk, n, hw, ad); }
-        if (GRAD) lds_load_addend<NC>(p, tx, tyk, n, hw, ad);              // the upstream gradient of the tile, ahead of the younger loads
+        if (GRAD) lds_load_addend<NC, TS>(p, tx, tyk, n, hw, ad);          // the upstream gradient of the tile (stored as the source is), ahead of the younger loads
         if (k + 1 < T) {
             if (more) lds_issue<NC, VALID, SUB, TS>(p, sb, sm, hw, Bx[k + 1], S, sbb);   // the next tile's staging loads fly while this one is gathered and stored
         }
@@ -1246,6 +1253,7 @@ template <int T, int NC, bool VALID, int ADD = 0, bool SUB = false, bool DF = fa
 __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_rows_kernel(const WarpParams p_by_value) {
     static_assert((ADD == 0 && !SUB && !DF) || NC == 2, "ADD / SUB / DF: flows");
     static_assert(!GRAD || (!VALID && ADD == 0 && !SUB && !DF), "GRAD: plain taps");
+    typedef typename std::conditional<GRAD, TS, float>::type TGA;          // (GRAD: the upstream gradient is stored as the source is; an addend is fp32)
     typedef typename std::conditional<ROUND, WarpParamsK, WarpParamsLeanK>::type WPK;
     WPK* pp = (WPK*)__builtin_amdgcn_kernarg_segment_ptr();
 #define p (*pp)
@@ -1338,7 +1346,7 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_rows_kernel(const WarpPara
         if (k + 1 < T) {
             rows_scan(p, rt.tmin[(k + 1) & 1], rt.tmax[(k + 1) & 1], rt.ent[(k + 1) & 1], rt.start[(k + 1) & 1], org[k + 1], cxo[k + 1], Gx[k + 1], R);
             OFL_RS(5);
-            if (ADD == 2 || GRAD) lds_load_addend<NC>(p, tx, tyk, n, hw, ad);   // (ahead of the younger staging loads: waited for without them)
+            if (ADD == 2 || GRAD) lds_load_addend<NC, TGA>(p, tx, tyk, n, hw, ad);   // (ahead of the younger staging loads: waited for without them)
             rows_issue<NC, VALID, SUB, TS>(p, sb, sm, hw, Gx[k + 1], R, rt.start[(k + 1) & 1], S, sbb);
             OFL_RS(6);
         }
@@ -1347,7 +1355,7 @@ __global__ __launch_bounds__(kLdsNT, 3) void warp_bwd_rows_kernel(const WarpPara
         f4 outv[4];
         if (REFORM) lds_coords_box_a<false>(p, tx, tyk, uu[k], vv[k], 0, Tc[0], (int (*)[4])nullptr);
         if (ADD == 1) { ad[0] = uu[k]; ad[NC - 1] = vv[k]; }
-        if ((ADD == 2 || GRAD) && k + 1 >= T) lds_load_addend<NC>(p, tx, tyk, n, hw, ad);
+        if ((ADD == 2 || GRAD) && k + 1 >= T) lds_load_addend<NC, TGA>(p, tx, tyk, n, hw, ad);
         lds_gather<NC, VALID, SUB, TS, GRAD, false, typename std::remove_reference<decltype(p)>::type, true>(p, hw, sb, sm, Tc[REFORM ? 0 : k], B, smem, outv, sbb, GRAD ? ad : nullptr);
         OFL_RS(7);
         if (GRAD) { const f4 none[2] = {}; lds_store<2, false, false, false, float>(p, tx, tyk, n, hw, 0u, outv, none); }
@@ -1901,8 +1909,10 @@ __device__ __forceinline__ void splat_fwd_tiles(const SplatParams& p) {
     const int planes = 1 + C + (p.with_mask_chan ? 1 : 0);
     const float wmax = (float)(w - 1), hmax = (float)(h - 1);
 
-    const TF* __restrict__ fu = p.flow ? reinterpret_cast<const TF*>(p.flow) + n * p.flow_bs : nullptr;
-    const TF* __restrict__ db = reinterpret_cast<const TF*>(p.data) + n * p.data_bs;
+    typedef typename sp_el<TF>::flow TFL;
+    typedef typename sp_el<TF>::data TDA;
+    const TFL* __restrict__ fu = p.flow ? reinterpret_cast<const TFL*>(p.flow) + n * p.flow_bs : nullptr;
+    const TDA* __restrict__ db = reinterpret_cast<const TDA*>(p.data) + n * p.data_bs;
     const float* __restrict__ dbb = p.data_b ? p.data_b + n * p.data_b_bs : nullptr;
     const uint8_t* __restrict__ wmk = p.weight_mask ? p.weight_mask + n * p.weight_mask_bs : nullptr;
     const uint8_t* __restrict__ cma = p.chan_mask_a ? p.chan_mask_a + n * p.chan_mask_a_bs : nullptr;
@@ -1992,8 +2002,10 @@ __device__ __forceinline__ void splat_finalize_tiles(const SplatParams& p) {
     const int C = CT ? CT : p.c;
     const int planes = 1 + C + (p.with_mask_chan ? 1 : 0);
 
-    const TF* __restrict__ fu = p.flow ? reinterpret_cast<const TF*>(p.flow) + n * p.flow_bs : nullptr;
-    const TF* __restrict__ db = reinterpret_cast<const TF*>(p.data) + n * p.data_bs;
+    typedef typename sp_el<TF>::flow TFL;
+    typedef typename sp_el<TF>::data TDA;
+    const TFL* __restrict__ fu = p.flow ? reinterpret_cast<const TFL*>(p.flow) + n * p.flow_bs : nullptr;
+    const TDA* __restrict__ db = reinterpret_cast<const TDA*>(p.data) + n * p.data_bs;
     const float* __restrict__ dbb = p.data_b ? p.data_b + n * p.data_b_bs : nullptr;
     const uint8_t* __restrict__ wmk = p.weight_mask ? p.weight_mask + n * p.weight_mask_bs : nullptr;
     const uint8_t* __restrict__ cma = p.chan_mask_a ? p.chan_mask_a + n * p.chan_mask_a_bs : nullptr;
@@ -2219,7 +2231,8 @@ __device__ __forceinline__ void sp_finish_src(const SP& s, int sx4, int sy, bool
 
 template <typename TF = float, typename SP>
 __device__ __forceinline__ void sp_load_src(const SP& s, int n, int sx4, int sy, bool inimg, uint32_t pix, uint32_t hw, SpSrc& q) {
-    const TF* __restrict__ flw = reinterpret_cast<const TF*>(s.flow);     // (fp16 variants: the flow planes hold halves)
+    typedef typename sp_el<TF>::flow TFL;
+    const TFL* __restrict__ flw = reinterpret_cast<const TFL*>(s.flow);     // (fp16 variants: the flow planes hold halves)
     f4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
     uint32_t wm4 = 0x01010101u;
     // the last group of a row of an image whose width is not a multiple of 4: fetch the last whole group and rotate
@@ -2262,7 +2275,8 @@ __device__ __forceinline__ void sp_load_src(const SP& s, int n, int sx4, int sy,
 struct SpRaw { f4 a, b; uint32_t wm4; int rot; };
 template <typename TF = float, typename SP>
 __device__ __forceinline__ void sp_issue_src(const SP& s, int n, int sx4, int sy, bool inimg, uint32_t pix, uint32_t hw, SpRaw& r) {
-    const TF* __restrict__ flw = reinterpret_cast<const TF*>(s.flow);
+    typedef typename sp_el<TF>::flow TFL;
+    const TFL* __restrict__ flw = reinterpret_cast<const TFL*>(s.flow);
     r.a = (f4){0.f, 0.f, 0.f, 0.f}; r.b = (f4){0.f, 0.f, 0.f, 0.f};
     r.wm4 = 0x01010101u;
     const int wrem = OFL_SP_WREM(s);
@@ -2486,7 +2500,8 @@ struct SpTile {
 
 template <typename TF = float, typename SP>
 __device__ __forceinline__ void sp_tile_setup(const SP& s, int tx, int ty, int n, SpTile& t) {
-    const TF* __restrict__ flw = reinterpret_cast<const TF*>(s.flow);
+    typedef typename sp_el<TF>::flow TFL;
+    const TFL* __restrict__ flw = reinterpret_cast<const TFL*>(s.flow);
     const int tid = threadIdx.x, w = s.w, h = s.h;
     const uint32_t hw = (uint32_t)(h * w);
     t.n = n; t.dx0 = tx * kSpTW; t.dy0 = ty * kSpTH;
@@ -2534,8 +2549,9 @@ __device__ __forceinline__ void sp_finalize(const SP& s, const SpTile& t, const 
     // thread and tile, 2 GB of scratch writes per launch (rocprofv3 WRITE_SIZE: profiles/r2_splat_gather_first_cut_pmc.txt)
     uint32_t pix = t.pix;
     asm volatile("" : "+v"(pix));
-    static_assert(std::is_same<TO, float>::value || NC == 2, "fp16 outputs are flows");
-    const TF* __restrict__ db = reinterpret_cast<const TF*>(s.data) + n * s.data_bs;
+    static_assert(std::is_same<TO, float>::value || NC == 2 || !std::is_same<TO, _Float16>::value, "fp16 outputs (_Float16) are flows");
+    typedef typename sp_el<TF>::data TDA;
+    const TDA* __restrict__ db = reinterpret_cast<const TDA*>(s.data) + n * s.data_bs;
     const float* __restrict__ dbb = s.data_b ? s.data_b + n * s.data_b_bs : nullptr;
     f2 den2, out[NC], mch2;
     uint32_t warped2 = 0, valid2 = 0;
@@ -2644,7 +2660,8 @@ __device__ __forceinline__ void sp_finalize(const SP& s, const SpTile& t, const 
 template <int NC, bool MCH, typename TF = float, typename SP>
 __device__ __forceinline__ void sp_load_data(const SP& s, int n, int sx4, int sy, uint32_t hw, f4 (&dat)[NC], uint32_t& mc4) {
     const int w = s.w;
-    const TF* __restrict__ db = reinterpret_cast<const TF*>(s.data) + n * s.data_bs;
+    typedef typename sp_el<TF>::data TDA;
+    const TDA* __restrict__ db = reinterpret_cast<const TDA*>(s.data) + n * s.data_bs;
     const float* __restrict__ dbb = s.data_b ? s.data_b + n * s.data_b_bs : nullptr;
     const int wrem = OFL_SP_WREM(s);
     const bool edge = wrem != 0 && sx4 > w - 4;                   // row-end group: last whole group, rotated
@@ -2684,7 +2701,8 @@ template <int NC> struct SpRawData { f4 dat[NC], sub[NC <= 2 ? NC : 1]; uint32_t
 template <int NC, bool MCH, typename TF = float, typename SP>
 __device__ __forceinline__ void sp_issue_data(const SP& s, int n, int sx4, int sy, uint32_t hw, SpRawData<NC>& r) {
     const int w = s.w;
-    const TF* __restrict__ db = reinterpret_cast<const TF*>(s.data) + n * s.data_bs;
+    typedef typename sp_el<TF>::data TDA;
+    const TDA* __restrict__ db = reinterpret_cast<const TDA*>(s.data) + n * s.data_bs;
     const float* __restrict__ dbb = s.data_b ? s.data_b + n * s.data_b_bs : nullptr;
     const int wrem = OFL_SP_WREM(s);
     const bool edge = wrem != 0 && sx4 > w - 4;                   // row-end group: last whole group, rotated
@@ -3780,6 +3798,18 @@ static int splat_launch_diet(const GatherParams* gp, unsigned grid, hipStream_t 
     return (int)hipGetLastError();
 }
 static int splat_diet_dispatch(const GatherParams* gp, int nc, int mch, int elem, unsigned grid, hipStream_t st, int extra_lds, int lean, int32_t* info) {
+    if (elem == 3 || elem == 4) {                     // ofl_splat_sum_x16: an fp32 flow, 16-bit data and dst
+        if (mch) return OFL_E_UNSUPPORTED;
+#define OFL_DIET_X16(NC) (elem == 3 ? splat_launch_diet<NC, false, SpMixed<half_t>, half_t>(gp, grid, st, extra_lds, lean, info) \
+                                    : splat_launch_diet<NC, false, SpMixed<bf16_t>, bf16_t>(gp, grid, st, extra_lds, lean, info))
+        switch (nc) {
+            case 1: return OFL_DIET_X16(1);
+            case 2: return OFL_DIET_X16(2);
+            case 3: return OFL_DIET_X16(3);
+        }
+#undef OFL_DIET_X16
+        return OFL_E_UNSUPPORTED;
+    }
     if (elem != 0) {
         if (nc != 2) return OFL_E_UNSUPPORTED;
         if (mch) return elem == 2 ? splat_launch_diet<2, true, _Float16, _Float16>(gp, grid, st, extra_lds, lean, info) : splat_launch_diet<2, true, _Float16, float>(gp, grid, st, extra_lds, lean, info);
@@ -3801,7 +3831,7 @@ int ofl_splat_launch_gather_diet(const void* params, int nc, int mch, int elem, 
 extern "C" __attribute__((visibility("default"))) int ofl_splat_gather_info(int32_t channels, int32_t with_mask_chan, int32_t elem, int32_t lean,
                                                                             int32_t extra_lds, int32_t* info4) {
     if (!info4) return OFL_E_NULL;
-    if (channels < 1 || channels > 3 || elem < 0 || elem > 2 || extra_lds < 0) return OFL_E_ARG;
+    if (channels < 1 || channels > 3 || elem < 0 || elem > 4 || extra_lds < 0) return OFL_E_ARG;
     return splat_diet_dispatch(nullptr, channels, with_mask_chan ? 1 : 0, elem, 0, nullptr, extra_lds, lean, info4);
 }
 #elif defined(OFL_WIDE_TU)
@@ -4040,6 +4070,108 @@ extern "C" __attribute__((visibility("default"))) int ofl_warp_bwd_x16(
     p.dst_bs = (int64_t)c * h * w;
     return dtype == OFL_X16_HALF ? x16_launch<half_t>(p, src, dst, (hipStream_t)stream) : x16_launch<bf16_t>(p, src, dst, (hipStream_t)stream);
 }
+
+// ---- ofl_warp_bwd_grad_x16: the gradient of that warp with respect to its FLOW, from the 16-bit source and the 16-bit upstream gradient ----
+// Up to 3 planes: the GRAD instantiations of the staged kernels on TS = half_t / bf16_t (taps and upstream gradient up-converted at the
+// load, the fp32 sums of lds_gather_impl, fp32 grad_flow), picked as ofl_internal_warp_grad_flow_lds picks the fp32 ones -- row tables
+// with 1 / 2 / 4 tiles per block where the launch is lean, else the four-tile column kernel on the sheared rectangle.  More planes: the
+// sums run over ALL planes in one chain per pixel (the order of warp_grad_kernel, ofl_aux_kernels.hip, which the fp32 entry point takes
+// there), so they cannot be split into launches of 3: one pixel per lane, the same expressions, 2-byte gathers.
+namespace {
+template <typename TX>
+__global__ __launch_bounds__(256) void warp_grad_flow_x16_kernel(const float* __restrict__ flow, int64_t flow_bs, float flow_sign,
+                                                                 const TX* __restrict__ src, int64_t src_bs, const TX* __restrict__ gout,
+                                                                 float g_scale, float* __restrict__ gflow, int32_t c, int32_t h, int32_t w) {
+    const int n = blockIdx.y;
+    const int64_t hw = (int64_t)h * w;
+    const float wm1 = (float)(w - 1), hm1 = (float)(h - 1), half_wm1 = wm1 / 2.0f, half_hm1 = hm1 / 2.0f;
+    const float* __restrict__ fu = flow + n * flow_bs;
+    const TX* __restrict__ sb = src + n * src_bs;
+    const TX* __restrict__ gb = gout + (int64_t)n * c * hw;
+    float* __restrict__ gf = gflow + (int64_t)n * 2 * hw;
+    for (int64_t pix = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pix < hw; pix += (int64_t)gridDim.x * blockDim.x) {
+        const int y = (int)(pix / w), x = (int)(pix - (int64_t)y * w);
+        const float sx = unnormalise((float)x - flow_sign * fu[pix], wm1, half_wm1);
+        const float sy = unnormalise((float)y - flow_sign * fu[hw + pix], hm1, half_hm1);
+        // the four taps: fractions, validity, offsets clamped into the plane (make_taps of ofl_aux_kernels.hip)
+        const float x_w = floorf(sx), y_n = floorf(sy), x_e = x_w + 1.0f, y_s = y_n + 1.0f;
+        const float ww = sx - x_w, e = 1.0f - ww, nn = sy - y_n, s = 1.0f - nn;
+        const bool x0 = (x_w > -1.0f) && (x_w < (float)w), x1 = (x_e > -1.0f) && (x_e < (float)w);
+        const bool y0 = (y_n > -1.0f) && (y_n < (float)h), y1 = (y_s > -1.0f) && (y_s < (float)h);
+        const int ix0 = x0 ? (int)x_w : 0, ix1 = x1 ? (int)x_e : 0, iy0 = y0 ? (int)y_n : 0, iy1 = y1 ? (int)y_s : 0;
+        const int64_t o_nw = (int64_t)iy0 * w + ix0, o_ne = (int64_t)iy0 * w + ix1, o_sw = (int64_t)iy1 * w + ix0, o_se = (int64_t)iy1 * w + ix1;
+        float gix = 0.0f, giy = 0.0f;
+        for (int ch = 0; ch < c; ++ch) {
+            const float g = g_scale * ld1(gb + (int64_t)ch * hw + pix);
+            const TX* __restrict__ sp = sb + (int64_t)ch * hw;
+            const float v_nw = (x0 && y0) ? ld1(sp + o_nw) : 0.0f, v_ne = (x1 && y0) ? ld1(sp + o_ne) : 0.0f;
+            const float v_sw = (x0 && y1) ? ld1(sp + o_sw) : 0.0f, v_se = (x1 && y1) ? ld1(sp + o_se) : 0.0f;
+            gix -= v_nw * s * g; gix += v_ne * s * g; gix -= v_sw * nn * g; gix += v_se * nn * g;
+            giy -= v_nw * e * g; giy -= v_ne * ww * g; giy += v_sw * e * g; giy += v_se * ww * g;
+        }
+        gf[pix] = -flow_sign * (((gix * half_wm1) / wm1) * 2.0f);
+        gf[hw + pix] = -flow_sign * (((giy * half_hm1) / hm1) * 2.0f);
+    }
+}
+
+template <typename TX, int NC>
+int x16_grad_staged(const WarpParams& p, hipStream_t st) {
+    WarpParams q = p;
+    const unsigned g1 = x16_tiles(p, 32, 16), g4 = x16_tiles(p, 32, 64);
+    constexpr int TT = kLdsT > 2 ? kLdsT : 3, RT = OFL_ROWS_T;
+    if (warp_is_lean(q)) {
+        const int tt = g4 >= OFL_ROWS_T4_MIN ? RT : (g1 < OFL_ROWS_T1_MAX ? 1 : 2);
+        const unsigned gr = warp_geometry(q, kLdsTWQ * 4, tt * kLdsTH);
+#define OFL_X16_RG(T_) OFL_KLAUNCH((warp_bwd_rows_kernel<T_, NC, false, 0, false, false, TX, float, false, true>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, st, q)
+        if (tt == 1) OFL_X16_RG(1); else if (tt == 2) OFL_X16_RG(2); else OFL_X16_RG(RT);
+#undef OFL_X16_RG
+        return (int)hipGetLastError();
+    }
+    const unsigned g = warp_geometry(q, kLdsTWQ * 4, TT * kLdsTH);
+    OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, NC, false, false, false, false, TX, float, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+    return (int)hipGetLastError();
+}
+template <typename TX>
+int x16_grad_launch(const WarpParams& p, float* grad_flow, hipStream_t st) {
+    if (p.c <= 3) return p.c == 1 ? x16_grad_staged<TX, 1>(p, st) : p.c == 2 ? x16_grad_staged<TX, 2>(p, st) : x16_grad_staged<TX, 3>(p, st);
+    const int64_t hw = (int64_t)p.h * p.w;
+    int64_t bx = (hw + 255) / 256, cap = 8192 / p.n;           // (the grid of warp_grad_kernel: blocks_for, ofl_aux_kernels.hip)
+    cap = cap < 64 ? 64 : cap;
+    if (bx > cap) bx = cap;
+    OFL_KLAUNCH((warp_grad_flow_x16_kernel<TX>), dim3((unsigned)bx, (unsigned)p.n), dim3(256), 0, st, p.flow, p.flow_bs, p.flow_sign,
+                reinterpret_cast<const TX*>(p.src), p.src_bs, reinterpret_cast<const TX*>(p.addend), p.g_sign, grad_flow, p.c, p.h, p.w);
+    return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("default"))) int ofl_warp_bwd_grad_x16(
+    const float* flow, int64_t flow_bs, float flow_sign, const void* src, int64_t src_bs, const void* grad_out, float g_scale,
+    float* grad_flow, int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype, void* stream) {
+    if (!flow || !src || !grad_out || !grad_flow) return OFL_E_NULL;
+    int rc = check_dims(n, c, h, w, false);
+    if (rc) return rc;
+    if (n > 65535) return OFL_E_SHAPE;
+    if (dtype != OFL_X16_HALF && dtype != OFL_X16_BFLOAT) return OFL_E_ARG;
+    if (!(flow_sign == 1.0f || flow_sign == -1.0f)) return OFL_E_ARG;
+    if (flow_bs < 0 || src_bs < 0) return OFL_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(grad_out)) & 1u) return OFL_E_ARG;
+    if ((int64_t)((w + 31) / 32) * ((h + 15) / 16) * n >= (1ll << 31)) return OFL_E_SHAPE;
+    // the frames of the staged kernels, on the automatic path (what ofl_warp_bwd_grad_f32 gives its one-pixel-per-lane kernel for the
+    // FRAME's sake -- W < 4, H < 2, 2^24 pixels -- is declined: the caller converts and calls it)
+    if (!(ofl_warp_path_option() == 0 && w >= 4 && h >= 2 && w < 32760 && h < 32760 && (int64_t)h * w < (1ll << 24))) return OFL_E_UNSUPPORTED;
+    WarpParams p = {};
+    p.flow = flow; p.flow_bs = flow_bs; p.src = reinterpret_cast<const float*>(src); p.src_bs = src_bs;
+    p.addend = reinterpret_cast<const float*>(grad_out); p.addend_bs = (int64_t)c * h * w;      // (the kernels re-read both as 16-bit planes)
+    p.dst = grad_flow; p.dst_bs = (int64_t)2 * h * w;
+    p.n = n; p.c = c; p.h = h; p.w = w;
+    p.flow_sign = flow_sign; p.a_sign = 1.0f; p.g_sign = g_scale; p.round_mode = OFL_ROUND_NONE;
+    p.wm1 = (float)(w - 1); p.hm1 = (float)(h - 1);
+    p.half_wm1 = p.wm1 / 2.0f; p.half_hm1 = p.hm1 / 2.0f;
+    p.rcp_wm1 = 1.0f / p.wm1; p.rcp_hm1 = 1.0f / p.hm1;
+    p.lds_bytes = kLdsBytes;
+    p.shear = (ofl_warp_shear_option() && (int64_t)h + 4 * (int64_t)w + 8 < 32760) ? 1 : 0;
+    return dtype == OFL_X16_HALF ? x16_grad_launch<half_t>(p, grad_flow, (hipStream_t)stream) : x16_grad_launch<bf16_t>(p, grad_flow, (hipStream_t)stream);
+}
 #else
 int g_warp_path = 0;   // ofl_set_option(OFL_OPT_WARP_PATH, .): 0 auto, 1 generic direct-gather kernel only, 2 (= auto), 3 / 4 staged with two tiles / one tile per block whatever the launch size (tests), 5 = auto but more than 3 channels as separate launches of 3 (tests: the channel-loop kernel against them), 6 = auto but the sheared rectangle instead of per-row extents (tests, A/B), 7 = auto but plain lean launches on four-tile row-table columns whatever the size (tests)
 int g_warp_shear = 1;   // ofl_set_option(OFL_OPT_WARP_SHEAR, .)
@@ -4220,7 +4352,7 @@ int launch_warp(const WarpParams& p, unsigned grid, hipStream_t st) {
 // device and instantiation, cached; one block per CU fewer than the API says where it says more than one (the API is one high
 // for some register counts: MI355X_MICROARCH.md, residency); never above kFallbackBlocks, never below 1.
 inline unsigned fallback_resident_blocks(const void* kernel, int which) {
-    static int cache[64][5];                                  // 0 = not asked yet (a benign race: every asker stores the same number)
+    static int cache[64][11];                                  // 0 = not asked yet (a benign race: every asker stores the same number)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
     int v = cache[dev][which];
@@ -4677,8 +4809,10 @@ static int splat_tiled_impl(
     int32_t with_mask_chan, int32_t occlude, float* dst, float* density, uint8_t* warped, uint8_t* valid,
     float* mask_chan, int32_t* dst_flags, int32_t* workspace, int64_t workspace_ints, float* accum_fallback, int32_t n,
     int32_t c, int32_t h, int32_t w, int32_t round_mode, void* stream, int32_t fh, int32_t fw, int32_t foy, int32_t fox, int elem = 0, int raw = 0) {
-    const bool half_in = elem != 0;       // flow and data planes hold fp16 (2 channels, no window, no xs / ys, no data_b, no rounding)
+    const bool half_in = elem == 1 || elem == 2;       // flow and data planes hold fp16 (2 channels, no window, no xs / ys, no data_b, no rounding)
+    const bool x16 = elem == 3 || elem == 4;            // fp32 flow, data and dst planes hold fp16 / bf16 (ofl_splat_sum_x16: raw sums, no masks, no density)
     if (!data || !dst || !workspace || !accum_fallback) return OFL_E_NULL;
+    if (x16 && (!flow || xs || ys || data_b || fw != 0 || round_mode != 0 || with_mask_chan || density || warped || dst_flags)) return OFL_E_UNSUPPORTED;
     if (half_in && (c != 2 || !flow || xs || ys || data_b || fw != 0 || round_mode != 0)) return OFL_E_UNSUPPORTED;
     if (!flow && !(xs && ys)) return OFL_E_NULL;
     if (flow && !(flow_sign == 1.0f || flow_sign == -1.0f)) return OFL_E_ARG;
@@ -4735,9 +4869,11 @@ static int splat_tiled_impl(
         SplatParams base = all;
         base.n = (int32_t)nn;
         // (fp16 variants: the flow / data / dst pointers address halves -- advance them in their own element size)
-        auto adv_in = [&](const float* ptr, int64_t elems) { return half_in ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(ptr) + elems) : ptr + elems; };
-        auto adv_out = [&](float* ptr, int64_t elems) { return elem == 2 ? reinterpret_cast<float*>(reinterpret_cast<_Float16*>(ptr) + elems) : ptr + elems; };
-        if (base.flow) base.flow = adv_in(all.flow, n0 * all.flow_bs);
+        auto adv16 = [](const float* ptr, int64_t elems) { return reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(ptr) + elems); };
+        auto adv_flow = [&](const float* ptr, int64_t elems) { return half_in ? adv16(ptr, elems) : ptr + elems; };
+        auto adv_in = [&](const float* ptr, int64_t elems) { return (half_in || x16) ? adv16(ptr, elems) : ptr + elems; };
+        auto adv_out = [&](float* ptr, int64_t elems) { return (elem == 2 || x16) ? const_cast<float*>(adv16(ptr, elems)) : ptr + elems; };
+        if (base.flow) base.flow = adv_flow(all.flow, n0 * all.flow_bs);
         if (base.xs) { base.xs = all.xs + n0 * all.xy_bs; base.ys = all.ys + n0 * all.xy_bs; }
         base.data = adv_in(all.data, n0 * all.data_bs);
         if (base.data_b) base.data_b = all.data_b + n0 * all.data_b_bs;
@@ -4771,7 +4907,7 @@ static int splat_tiled_impl(
         for (int32_t c0 = 0; c0 < c; c0 += 3) {
             SplatParams full = base;
             full.c = (c - c0) < 3 ? (c - c0) : 3;
-            full.data = base.data + c0 * hw; full.dst = base.dst + c0 * hw;
+            full.data = adv_in(base.data, c0 * hw); full.dst = adv_out(base.dst, c0 * hw);
             if (base.data_b) full.data_b = base.data_b + c0 * hw;
             if (c0 > 0) { full.with_mask_chan = 0; full.density = nullptr; full.warped = nullptr; full.valid = nullptr; full.mask_chan = nullptr; }
             const int32_t cg = full.c;
@@ -4782,6 +4918,7 @@ static int splat_tiled_impl(
             }
             const unsigned grid = (unsigned)(gp.per_xcd * kXcds);
             if (half_in) rc = launch_splat_gather_half(gp, grid, st, elem);
+            else if (x16) rc = ofl_splat_launch_gather_diet(&gp, cg, 0, elem, grid, (void*)st, g_splat_extra_lds);
             else switch (cg) {
                 case 1: rc = launch_splat_gather<1>(gp, grid, st); break;
                 case 2: rc = launch_splat_gather<2>(gp, grid, st); break;
@@ -4803,16 +4940,23 @@ static int splat_tiled_impl(
             // (strided: the kernel walks the tiles of the flagged images; its passes meet at grid barriers, so the grid must be
             // RESIDENT AS A WHOLE: bounded by what the device -- a CPX partition, a CU-masked stream's device -- can hold, with
             // half of it left to whatever else runs, a second call's fallback kernel on another stream included)
-            const int which = half_in ? (elem == 2 ? 3 : 4) : (cg == 1 ? 0 : (cg == 2 ? 1 : 2));
-            const void* kfn = half_in ? (elem == 2 ? (const void*)splat_fallback_kernel<2, _Float16, _Float16> : (const void*)splat_fallback_kernel<2, _Float16, float>)
+            const int which = x16 ? 5 + 3 * (elem - 3) + (cg - 1) : half_in ? (elem == 2 ? 3 : 4) : (cg == 1 ? 0 : (cg == 2 ? 1 : 2));
+#define OFL_FB_X16(CT) (elem == 3 ? (const void*)splat_fallback_kernel<CT, SpMixed<half_t>, half_t> : (const void*)splat_fallback_kernel<CT, SpMixed<bf16_t>, bf16_t>)
+            const void* kfn = x16 ? (cg == 1 ? OFL_FB_X16(1) : (cg == 2 ? OFL_FB_X16(2) : OFL_FB_X16(3))) : half_in ? (elem == 2 ? (const void*)splat_fallback_kernel<2, _Float16, _Float16> : (const void*)splat_fallback_kernel<2, _Float16, float>)
                                       : (cg == 1 ? (const void*)splat_fallback_kernel<1> : (cg == 2 ? (const void*)splat_fallback_kernel<2> : (const void*)splat_fallback_kernel<3>));
+#undef OFL_FB_X16
             const unsigned resident = fallback_resident_blocks(kfn, which);
             if (g2 > resident) g2 = resident;
             for (int64_t r0 = 0; r0 < nn; r0 += fb.fb_slots) {
                 fb.fb_round = (int32_t)(r0 / fb.fb_slots);
                 int32_t* arrivals = gp.stats + 4;           // two words, zeroed with the statistics words at the start of the call and left zero by every launch
                 const int64_t cpi = (int64_t)planes * hw;
-                if (half_in) {
+                if (x16) {
+#define OFL_FB_X16_GO(CT) do { if (elem == 3) OFL_KLAUNCH((splat_fallback_kernel<CT, SpMixed<half_t>, half_t>), dim3(g2), dim3(256), 0, st, fb, accum_fallback, cpi, (int32_t)nn, arrivals); \
+                               else OFL_KLAUNCH((splat_fallback_kernel<CT, SpMixed<bf16_t>, bf16_t>), dim3(g2), dim3(256), 0, st, fb, accum_fallback, cpi, (int32_t)nn, arrivals); } while (0)
+                    switch (cg) { case 1: OFL_FB_X16_GO(1); break; case 2: OFL_FB_X16_GO(2); break; default: OFL_FB_X16_GO(3); break; }
+#undef OFL_FB_X16_GO
+                } else if (half_in) {
                     if (elem == 2) OFL_KLAUNCH((splat_fallback_kernel<2, _Float16, _Float16>), dim3(g2), dim3(256), 0, st, fb, accum_fallback, cpi, (int32_t)nn, arrivals);
                     else OFL_KLAUNCH((splat_fallback_kernel<2, _Float16, float>), dim3(g2), dim3(256), 0, st, fb, accum_fallback, cpi, (int32_t)nn, arrivals);
                 } else switch (cg) {
@@ -4882,6 +5026,22 @@ __attribute__((visibility("default"))) int ofl_splat_sum_f32(
     return splat_tiled_impl(flow, flow_bs, flow_sign, nullptr, nullptr, 0, data, data_bs, data_sign, nullptr, 0, nullptr, 0, nullptr, 0,
                             nullptr, 0, 0, 0, dst, nullptr, nullptr, nullptr, nullptr, nullptr, workspace, workspace_ints,
                             accum_fallback, n, c, h, w, 0, stream, 0, 0, 0, 0, 0, 1);
+}
+
+// ofl_splat_sum_f32 for a 16-bit `data` and `dst` (the gradient of ofl_warp_bwd_x16 with respect to its source): the fp32 flow, the
+// same kernels on SpMixed<half_t / bf16_t> data -- up-converted at the record loads, summed in fp32 in the same order, rounded to
+// nearest even ONCE, at the store that produces dst (the band launch and the fallback accumulator stay fp32)
+__attribute__((visibility("default"))) int ofl_splat_sum_x16(
+    const float* flow, int64_t flow_bs, float flow_sign, const void* data, int64_t data_bs, float data_sign, void* dst,
+    int32_t* workspace, int64_t workspace_ints, float* accum_fallback, int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype,
+    void* stream) {
+    if (!flow || !data || !dst) return OFL_E_NULL;
+    if (dtype != OFL_X16_HALF && dtype != OFL_X16_BFLOAT) return OFL_E_ARG;
+    if (!aligned_to(data, 2) || !aligned_to(dst, 2)) return OFL_E_ARG;
+    if (flow_bs < 0 || data_bs < 0) return OFL_E_ARG;
+    return splat_tiled_impl(flow, flow_bs, flow_sign, nullptr, nullptr, 0, static_cast<const float*>(data), data_bs, data_sign, nullptr, 0,
+                            nullptr, 0, nullptr, 0, nullptr, 0, 0, 0, static_cast<float*>(dst), nullptr, nullptr, nullptr, nullptr, nullptr,
+                            workspace, workspace_ints, accum_fallback, n, c, h, w, 0, stream, 0, 0, 0, 0, dtype == OFL_X16_HALF ? 3 : 4, 1);
 }
 
 __attribute__((visibility("default"))) int ofl_flow_flags_f32(const float* flow, int64_t flow_bs,
