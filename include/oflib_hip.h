@@ -458,6 +458,32 @@ int ofl_splat_sum_x16(const float* flow, int64_t flow_bs, float flow_sign,
                       int32_t* workspace, int64_t workspace_ints, float* accum_fallback,
                       int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype, void* stream);
 
+/*
+ * FEATURE TENSORS STORED N-H-W-C (Flow.apply / apply_flow 't' of a tensor in torch.channels_last, the memory format convolution
+ * networks are trained in on this hardware).  The plain backward warp of ofl_warp_bwd_f32 / ofl_warp_bwd_x16 on that storage: the
+ * four taps of a destination pixel are four runs of C contiguous elements, the destination is one streaming store, nothing is
+ * transposed before or after.  The arithmetic and its order are those of ofl_warp_bwd_f32 (taps outside the frame are not loaded and
+ * count as 0, in-bounds tests on floats); 16-bit elements are up-converted at the load (exact) and rounded ONCE, to nearest even, at
+ * the store, as in ofl_warp_bwd_x16.  Bit-identical to transposing, calling the planar entry point and transposing back.  No atomics.
+ *
+ *   ofl_warp_bwd_nhwc     flow fp32 planes [*,2,H,W] as everywhere else; src [*,H,W,C] and dst [N,H,W,C] (contiguous in that order)
+ *                         elements of `dtype` (OFL_NHWC_F32, OFL_X16_HALF, OFL_X16_BFLOAT); src_mask / flow_mask [*,H,W] and valid
+ *                         [N,H,W] (optional, layout-free) as in ofl_warp_bwd_f32; batch strides in elements, 0 broadcasts one flow /
+ *                         source / mask.  A lane owns 16 bytes of consecutive channels (4 with 16-bit elements when C % 8 != 0):
+ *                         with C < 4 or C % 4 != 0, H < 2 or W < 2, src or dst not aligned to 16 bytes (fp32) / 8 bytes (16-bit),
+ *                         N > 65535 or 2^32 lanes and more per image it returns OFL_E_UNSUPPORTED and launches nothing: take the
+ *                         planar entry point.  OFL_E_ARG for another dtype, negative strides or sizes, a flow_sign other than +-1;
+ *                         OFL_E_SHAPE for a zero size or H*W >= 2^31.  64-bit element offsets throughout (N*C*H*W may pass 2^31).
+ *                         ofl_last_kernel_name() then names `warp_bwd_nhwc_kernel<float | half_t | bf16_t, channels per lane, valid>`.
+ */
+#define OFL_NHWC_F32 2
+int ofl_warp_bwd_nhwc(const float* flow, int64_t flow_bs, float flow_sign,
+                      const void* src, int64_t src_bs,
+                      const uint8_t* src_mask, int64_t src_mask_bs,
+                      const uint8_t* flow_mask, int64_t flow_mask_bs,
+                      void* dst, uint8_t* valid,
+                      int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------------
  * Either side of the path: backward passes, point tracking, padding extents.

@@ -30,7 +30,13 @@ class WarpFn(torch.autograd.Function):
         d = lambda t: None if t is None else t.detach()
         kw = dict(kw)
         res = None
-        if kw.pop("keep16", False):
+        nhwc, keep16 = kw.pop("nhwc", False), kw.pop("keep16", False)
+        if nhwc:
+            # a feature tensor stored channels_last: the native N-H-W-C launch (the output is channels_last whether or not a gradient is
+            # wanted); a launch the library declines goes on below, on the planar route
+            res = _native._warp_bwd_nhwc(d(flow), d(src), addend=d(addend), src_b=d(src_b), **kw)
+        ctx.nhwc = res is not None
+        if res is None and keep16:
             # a feature tensor stored in fp16 / bf16: the native 16-bit launch, and the 16-BIT source is what is saved (the
             # backward up-converts it transiently for the fp32 backward kernels); a launch the library declines is converted
             # here, so that the output has the source's dtype either way
@@ -56,20 +62,27 @@ class WarpFn(torch.autograd.Function):
         need_flow, need_src, need_add, need_b = ctx.needs_input_grad[:4]
         dense = g.is_contiguous()                         # (a strided upstream gradient -- channels-last -- keeps the present route)
         g = g.contiguous()
+        as_stored = lambda t: t
+        if getattr(ctx, "nhwc", False):
+            # the forward ran on N-H-W-C storage: the saved source and the upstream gradient as planes, then the planar route's own
+            # backward kernels on the same values (a native N-H-W-C backward: DESIGN.md section 8); the source gradient goes back
+            # channels_last, as the source is stored
+            src, dense = src.contiguous(), True
+            as_stored = lambda t: t.contiguous(memory_format=torch.channels_last)
         if (dense and src.dtype in _native._X16_DTYPES and src.device.type == 'cuda' and g.dtype == src.dtype and src_b is None
                 and ctx.addend_meta is None and src.shape[0] == g.shape[0] and (need_flow or need_src)):
             # a 16-bit source that took the native forward: both gradients from the 16-bit planes (no fp32 copy of the source, of g or of
             # the source gradient); a source broadcast over the batch sums its gradient in fp32 below, as does a launch the library declines
             res = _native.warp_bwd_grad_x16(flow, src, g, flow_sign=flow_sign, g_scale=g_sign, want_src=bool(need_src), want_flow=bool(need_flow))
             if res is not None:
-                return (_reduce_to(res[1], flow) if need_flow else None), (res[0] if need_src else None), None, None, None
+                return (_reduce_to(res[1], flow) if need_flow else None), (as_stored(res[0]) if need_src else None), None, None, None
         gathered = src.detach().float()
         if src_b is not None:
             gathered = gathered.to(g.device) - src_b.detach().float().to(g.device)
         gs, gf = _native.warp_bwd_grad(flow, gathered, g, flow_sign=flow_sign, g_scale=g_sign,
                                        want_src=bool(need_src or need_b), want_flow=bool(need_flow))
         g_flow = _reduce_to(gf, flow) if need_flow else None
-        g_src = _reduce_to(gs, src) if need_src else None
+        g_src = as_stored(_reduce_to(gs, src)) if need_src else None
         g_b = _reduce_to(-gs, src_b) if (need_b and src_b is not None) else None
         g_add = None
         if need_add and ctx.addend_meta is not None:
@@ -88,14 +101,16 @@ def warp(flow, src, **kw):
         d = lambda t: None if t is None else t.detach()
         kw = dict(kw)
         kw.pop("keep16", None)
+        kw.pop("nhwc", None)
         kw["addend"], kw["src_b"] = d(kw.get("addend")), d(kw.get("src_b"))
         with _native._on(_native.device(flow, src)):
             return _native._warp_bwd_raw(flow.detach(), src.detach(), **kw)
     kw = dict(kw)
     addend, src_b = kw.pop("addend", None), kw.pop("src_b", None)
     kw.pop("out_uint8", None)
-    if kw.get("keep16") and not (addend is None and src_b is None):
-        kw.pop("keep16")
+    if not (addend is None and src_b is None):
+        kw.pop("keep16", None)
+        kw.pop("nhwc", None)
     if src.dtype == torch.uint8:          # (only the flow can want a gradient: the backward kernel reads float planes)
         src = src.float()
     return WarpFn.apply(flow, src, addend, src_b, kw)

@@ -7,7 +7,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 SOURCES = [os.path.join(_PKG, "csrc", "ofl_kernels.hip"), os.path.join(_PKG, "csrc", "ofl_aux_kernels.hip"), os.path.join(_PKG, "csrc", "ofl_splat_gather.hip"),
            os.path.join(_PKG, "csrc", "ofl_warp_wide.hip"), os.path.join(_PKG, "csrc", "ofl_visualise.hip"), os.path.join(_PKG, "csrc", "ofl_matrix.hip"),
-           os.path.join(_PKG, "csrc", "ofl_arrows.hip"), os.path.join(_PKG, "csrc", "ofl_mesh.hip"), os.path.join(_PKG, "csrc", "ofl_warp_half.hip")]
+           os.path.join(_PKG, "csrc", "ofl_arrows.hip"), os.path.join(_PKG, "csrc", "ofl_mesh.hip"), os.path.join(_PKG, "csrc", "ofl_warp_half.hip"),
+           os.path.join(_PKG, "csrc", "ofl_warp_nhwc.hip")]
 HEADERS = [os.path.join(_ROOT, "include", "oflib_hip.h")]
 LIB_PATH = os.path.join(_PKG, "libofl_hip.so")
 

@@ -31,7 +31,7 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_matrix_workspace_bytes", "ofl_matrix_fit_f64",
             "ofl_arrows_workspace_ints", "ofl_arrows_scale_f32", "ofl_arrows_plan", "ofl_arrows_u8",
             "ofl_mesh_workspace_ints", "ofl_mesh_plan", "ofl_mesh_apply", "ofl_mesh_points",
-            "ofl_warp_bwd_x16", "ofl_warp_bwd_grad_x16", "ofl_splat_sum_x16")
+            "ofl_warp_bwd_x16", "ofl_warp_bwd_grad_x16", "ofl_splat_sum_x16", "ofl_warp_bwd_nhwc")
 _lib = None
 
 
@@ -121,6 +121,7 @@ def load_library(path: str = None):
                                      i32, i32, i32, i32, i32, i32, p]
     lib.ofl_warp_bwd_grad_x16.argtypes = [p, i64, f32, p, i64, p, f32, p, i32, i32, i32, i32, i32, p]
     lib.ofl_splat_sum_x16.argtypes = [p, i64, f32, p, i64, f32, p, p, i64, p, i32, i32, i32, i32, i32, p]
+    lib.ofl_warp_bwd_nhwc.argtypes = [p, i64, f32, p, i64, p, i64, p, i64, p, p, i32, i32, i32, i32, i32, p]
     for name in _SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     lib.ofl_arrows_workspace_ints.restype = ctypes.c_int64
@@ -518,6 +519,75 @@ def warp_bwd_keep16(flow, src, **kw):
         from . import _autograd
         return _autograd.warp(flow, src, keep16=True, **kw)
     return _warp_bwd_x16(flow, src, **kw)
+
+
+_NHWC_DTYPES = {torch.float16: 0, torch.bfloat16: 1, torch.float32: 2}       # OFL_X16_HALF, OFL_X16_BFLOAT, OFL_NHWC_F32
+NHWC_MIN_CHANNELS = 4       # the channels_last route is taken from this C on (the threshold and the measurement behind it)
+
+
+def _nhwc_kind(t: torch.Tensor):
+    """The `dtype` argument of ofl_warp_bwd_nhwc for a tensor the channels_last kernel reads as it is stored, else None: 4-D, fp32 / fp16 /
+    bf16, dense in torch.channels_last and NOT in the default format (C = 1 and 1 x 1 frames, where the two coincide, keep the planar
+    route), C a multiple of 4, H and W >= 2, the data pointer aligned to a lane's vector (16 bytes fp32, 8 bytes 16-bit).  Pure: no
+    device needed."""
+    if t.dim() != 4 or t.dtype not in _NHWC_DTYPES:
+        return None
+    c, h, w = t.shape[1:]
+    if c < 4 or c % 4 != 0 or h < 2 or w < 2 or t.shape[0] < 1:
+        return None
+    if t.is_contiguous() or not t.is_contiguous(memory_format=torch.channels_last):
+        return None
+    if t.data_ptr() % (16 if t.dtype == torch.float32 else 8) != 0:
+        return None
+    return _NHWC_DTYPES[t.dtype]
+
+
+def _warp_bwd_nhwc(flow, src, *, flow_sign=1.0, src_mask=None, flow_mask=None, want_valid=False, addend=None, a_sign=1.0,
+                   g_sign=1.0, round_mode=ROUND_NONE, want_flags=False, want_src_flags=False, want_dst_flags=False,
+                   src_b=None, out_uint8=False):
+    """ofl_warp_bwd_nhwc: a feature tensor stored channels_last warped from and to that storage (no transposed copy before or after);
+    dst has the source's dtype and is channels_last-contiguous.  None when the launch is not of that kind (`_nhwc_kind`) or the library
+    declines it: the caller takes the planar route."""
+    kind = _nhwc_kind(src)
+    if (kind is None or src.device.type != 'cuda' or addend is not None or src_b is not None
+            or round_mode != ROUND_NONE or want_flags or want_dst_flags):
+        return None
+    lib, dev = load_library(), device(flow, src)
+    if src.device != dev:
+        return None
+    c, h, w = src.shape[1:]
+    n = max(flow.shape[0], src.shape[0], 1 if src_mask is None else src_mask.shape[0], 1 if flow_mask is None else flow_mask.shape[0])
+    if src.shape[0] != n and src.shape[0] != 1:
+        raise ValueError("oflibpytorch_amd: source batch size %d cannot broadcast to %d" % (src.shape[0], n))
+    with _on(dev):
+        f, fbs = _planes(flow, dev, torch.float32, n, "flow")
+        sm, smbs = (None, 0) if src_mask is None else _planes(src_mask, dev, torch.bool, n, "source mask")
+        fm, fmbs = (None, 0) if flow_mask is None else _planes(flow_mask, dev, torch.bool, n, "flow mask")
+        dst = torch.empty((n, c, h, w), dtype=src.dtype, device=dev, memory_format=torch.channels_last)
+        valid = torch.empty((n, h, w), dtype=torch.bool, device=dev) if want_valid else None
+        rc = lib.ofl_warp_bwd_nhwc(_ptr(f), fbs, float(flow_sign), _ptr(src), 0 if src.shape[0] == 1 else c * h * w, _ptr(sm), smbs,
+                                   _ptr(fm), fmbs, _ptr(dst), _ptr(valid), n, c, h, w, kind, _stream(dev))
+        if rc == -4:
+            return None
+        _check(rc, "ofl_warp_bwd_nhwc")
+    return dst, valid, None, None
+
+
+def warp_bwd_nhwc(flow, src, **kw):
+    """`warp_bwd` for the TENSOR target of Flow.apply / apply_flow 't' stored channels_last on the device (`_nhwc_kind`, from
+    NHWC_MIN_CHANNELS on): `_warp_bwd_nhwc`, with a grad_fn whose forward is the same kernel when something requires a gradient (the
+    backward runs the planar backward kernels and returns the source gradient channels_last).  None when the call is not of that kind
+    or the library declines the launch: the caller takes the planar route (`warp_bwd_keep16` / `warp_bwd`)."""
+    if src.device.type != 'cuda' or _nhwc_kind(src) is None or src.shape[1] < NHWC_MIN_CHANNELS:
+        return None
+    if kw.get("round_mode", ROUND_NONE) != ROUND_NONE or kw.get("addend") is not None or kw.get("src_b") is not None:
+        return None
+    if flow.dtype == torch.float16:
+        flow = flow.float()                       # (the warper itself is read as fp32: exact up-conversion, utils.py:118)
+    if _wants_grad(flow, src):
+        from . import _autograd
+        return _autograd.warp(flow, src, nhwc=True, keep16=src.dtype in _X16_DTYPES, **kw)
+    return _warp_bwd_nhwc(flow, src, **kw)
 
 
 def warp_bwd(flow, src, **kw):

@@ -767,7 +767,8 @@ class Flow(object):
         m_flow & m_self).  `mask_chan_b` ('s' only; the padded batch-1-target case of `_warp_padded`): the batch-1 flow mask
         that goes into the mask channel instead of this flow's own, and keeps an all-zero flow's result at batch 1.
         `keep16` ('t' only; a TENSOR target of `apply`): fp16 / bf16 data on the device is warped from and to its 16-bit planes
-        and `warped` comes back in that dtype (`_native.warp_bwd_keep16`)."""
+        and `warped` comes back in that dtype (`_native.warp_bwd_keep16`); fp32 / fp16 / bf16 data stored channels_last on the device
+        is warped from and to that storage and `warped` comes back channels_last in that dtype (`_native.warp_bwd_nhwc`)."""
         mesh = self._ref == 's' and _mesh_mode("Flow.apply(ref='s')")
         batch_flags = self._batch_flags()                                             # (one look at the cached word for both tests)
         if batch_flags & _native.FLAG_NONFINITE:                                      # utils.py:98
@@ -800,7 +801,11 @@ class Flow(object):
             warped, valid = self._warp_mesh(t, tmask, need_valid, consider_mask, round_mode, flow_sign, data_sign, t_minus, mask_chan_b)
         elif self._ref == 't':
             res = None
-            if keep16 and t_minus is None and t.dtype in _native._X16_DTYPES:
+            if keep16 and t_minus is None and round_mode == _native.ROUND_NONE:
+                # a channels_last feature tensor on the device: warped from and to its N-H-W-C storage (None: not of that kind)
+                res = _native.warp_bwd_nhwc(self._fv, t, src_mask=tmask, flow_mask=self._mask if need_valid else None,
+                                            want_valid=need_valid)
+            if res is None and keep16 and t_minus is None and t.dtype in _native._X16_DTYPES:
                 res = _native.warp_bwd_keep16(self._fv, t, src_mask=tmask, flow_mask=self._mask if need_valid else None,
                                               want_valid=need_valid, round_mode=round_mode)
             if res is None:

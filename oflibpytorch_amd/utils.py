@@ -459,7 +459,9 @@ def apply_flow(flow, target: torch.Tensor, ref: str, mask=None) -> torch.Tensor:
                          .format(flow.shape[0], t.shape[0]))
     rm = _round_mode(dtype)
     if ref == 't':
-        res = _native.warp_bwd_keep16(flow, t, round_mode=rm) if t.dtype in _native._X16_DTYPES else None   # (fp16 / bf16 targets: from and to their 16-bit planes)
+        res = _native.warp_bwd_nhwc(flow, t, round_mode=rm)       # (channels_last fp32 / fp16 / bf16 targets on the device: from and to their N-H-W-C storage)
+        if res is None and t.dtype in _native._X16_DTYPES:
+            res = _native.warp_bwd_keep16(flow, t, round_mode=rm)   # (fp16 / bf16 targets: from and to their 16-bit planes)
         out = (_native.warp_bwd(flow, t, round_mode=rm, out_uint8=True) if res is None else res)[0]
     else:
         if _mesh_mode("apply_flow(ref='s')"):
