@@ -484,6 +484,39 @@ int ofl_warp_bwd_nhwc(const float* flow, int64_t flow_bs, float flow_sign,
                       void* dst, uint8_t* valid,
                       int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype, void* stream);
 
+/*
+ * The BACKWARD pass of ofl_warp_bwd_nhwc without a transposed copy of the saved source or of the upstream gradient.
+ *
+ *   ofl_warp_bwd_grad_nhwc  the gradient with respect to the FLOW: the arguments of ofl_warp_bwd_grad_x16 with src [*,H,W,C] and
+ *                           grad_out [N,H,W,C] elements of `dtype` (OFL_NHWC_F32, OFL_X16_HALF, OFL_X16_BFLOAT), read as they are
+ *                           stored; grad_flow fp32 planes [N,2,H,W], written, not accumulated.  flow_bs 0: one flow for all images.
+ *                           One pixel per lane and ONE chain per pixel over the channels 0 .. C-1 -- the arithmetic, order and
+ *                           association of ofl_warp_bwd_grad_f32's one-pixel-per-lane kernel (g = g_scale * grad_out, eight updates
+ *                           per channel, a tap outside the frame counts as 0 and is not loaded, in-bounds tests on floats, then
+ *                           -flow_sign * (((gix * half_wm1) / wm1) * 2)), 16-bit elements up-converted exactly at the load: the
+ *                           result equals the planar entry points' on the transposed operands bit for bit.  No LDS, no atomics,
+ *                           64-bit element offsets.  OFL_E_UNSUPPORTED (nothing launched) with C < 4 or C % 4 != 0, H < 2 or W < 2,
+ *                           src or grad_out not aligned to 16 bytes (fp32) / 8 bytes (16-bit), N > 65535; OFL_E_ARG, OFL_E_SHAPE and
+ *                           OFL_E_NULL as ofl_warp_bwd_nhwc.  ofl_last_kernel_name() then names
+ *                           `warp_grad_flow_nhwc_kernel<float | half_t | bf16_t, channels per chunk>`.
+ *   ofl_nhwc_to_planes      bit copy of `elem_bytes`-sized elements (2 or 4, else OFL_E_ARG) from src [N,H,W,C] to dst [N,C,H,W];
+ *   ofl_planes_to_nhwc      the same from src [N,C,H,W] to dst [N,H,W,C].  A tile of pixels x channels (64 x 32 4-byte, 128 x 64
+ *                           2-byte elements) goes through LDS: 16-byte accesses on the N-H-W-C side (8 bytes with 2-byte elements
+ *                           and C % 8 != 0), element-sized accesses coalesced along the pixels on the plane side (H*W may be odd).
+ *                           The gradient with respect to the SOURCE uses them either side of ofl_splat_sum_f32 / _x16.  C any
+ *                           multiple of 4, else OFL_E_UNSUPPORTED, as with the N-H-W-C operand not aligned to 16 bytes (4-byte
+ *                           elements) / 8 bytes (2-byte), N > 65535 or C > 2 097 120.  The operands must not overlap (OFL_E_ARG, as
+ *                           for a plane operand not aligned to its element, negative sizes); OFL_E_SHAPE for a zero size or
+ *                           H*W >= 2^31.  64-bit offsets.  ofl_last_kernel_name() then names
+ *                           `nhwc_transpose_kernel<unsigned int | unsigned short, elements per access, to planes>`.
+ */
+int ofl_warp_bwd_grad_nhwc(const float* flow, int64_t flow_bs, float flow_sign,
+                           const void* src, int64_t src_bs,
+                           const void* grad_out, float g_scale, float* grad_flow,
+                           int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype, void* stream);
+int ofl_nhwc_to_planes(const void* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t elem_bytes, void* stream);
+int ofl_planes_to_nhwc(const void* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t elem_bytes, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------------
  * Either side of the path: backward passes, point tracking, padding extents.

@@ -60,13 +60,20 @@ class WarpFn(torch.autograd.Function):
         flow, src, src_b = ctx.saved_tensors
         flow_sign, a_sign, g_sign = ctx.signs
         need_flow, need_src, need_add, need_b = ctx.needs_input_grad[:4]
-        dense = g.is_contiguous()                         # (a strided upstream gradient -- channels-last -- keeps the present route)
+        if getattr(ctx, "nhwc", False) and src_b is None and ctx.addend_meta is None and (need_flow or need_src):
+            # the forward ran on N-H-W-C storage and the upstream gradient arrived channels_last too: the flow gradient from both as they
+            # are stored, the source gradient through the library's own layout copies (DESIGN.md 3.14 "Autograd"); a planar gradient, a
+            # source broadcast over the batch or a launch the library declines goes on below
+            res = _native.warp_bwd_grad_nhwc(flow, src, g, flow_sign=flow_sign, g_scale=g_sign, want_src=bool(need_src), want_flow=bool(need_flow))
+            if res is not None:
+                return (_reduce_to(res[1], flow) if need_flow else None), (res[0] if need_src else None), None, None, None
+        dense = g.is_contiguous()                        # (a strided upstream gradient -- channels-last -- keeps the present route)
         g = g.contiguous()
         as_stored = lambda t: t
         if getattr(ctx, "nhwc", False):
-            # the forward ran on N-H-W-C storage: the saved source and the upstream gradient as planes, then the planar route's own
-            # backward kernels on the same values (a native N-H-W-C backward: DESIGN.md section 8); the source gradient goes back
-            # channels_last, as the source is stored
+            # the forward ran on N-H-W-C storage but the upstream gradient is not of that kind (or the launch was declined above): the saved
+            # source and the gradient as planes, then the planar route's own backward kernels on the same values; the source gradient goes
+            # back channels_last, as the source is stored
             src, dense = src.contiguous(), True
             as_stored = lambda t: t.contiguous(memory_format=torch.channels_last)
         if (dense and src.dtype in _native._X16_DTYPES and src.device.type == 'cuda' and g.dtype == src.dtype and src_b is None

@@ -31,7 +31,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_matrix_workspace_bytes", "ofl_matrix_fit_f64",
             "ofl_arrows_workspace_ints", "ofl_arrows_scale_f32", "ofl_arrows_plan", "ofl_arrows_u8",
             "ofl_mesh_workspace_ints", "ofl_mesh_plan", "ofl_mesh_apply", "ofl_mesh_points",
-            "ofl_warp_bwd_x16", "ofl_warp_bwd_grad_x16", "ofl_splat_sum_x16", "ofl_warp_bwd_nhwc")
+            "ofl_warp_bwd_x16", "ofl_warp_bwd_grad_x16", "ofl_splat_sum_x16", "ofl_warp_bwd_nhwc",
+            "ofl_warp_bwd_grad_nhwc", "ofl_nhwc_to_planes", "ofl_planes_to_nhwc")
 _lib = None
 
 
@@ -122,6 +123,9 @@ def load_library(path: str = None):
     lib.ofl_warp_bwd_grad_x16.argtypes = [p, i64, f32, p, i64, p, f32, p, i32, i32, i32, i32, i32, p]
     lib.ofl_splat_sum_x16.argtypes = [p, i64, f32, p, i64, f32, p, p, i64, p, i32, i32, i32, i32, i32, p]
     lib.ofl_warp_bwd_nhwc.argtypes = [p, i64, f32, p, i64, p, i64, p, i64, p, p, i32, i32, i32, i32, i32, p]
+    lib.ofl_warp_bwd_grad_nhwc.argtypes = [p, i64, f32, p, i64, p, f32, p, i32, i32, i32, i32, i32, p]
+    lib.ofl_nhwc_to_planes.argtypes = [p, p, i32, i32, i32, i32, i32, p]
+    lib.ofl_planes_to_nhwc.argtypes = [p, p, i32, i32, i32, i32, i32, p]
     for name in _SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     lib.ofl_arrows_workspace_ints.restype = ctypes.c_int64
@@ -942,17 +946,116 @@ def warp_bwd_grad_x16(flow, src16, grad_out16, *, flow_sign=1.0, g_scale=1.0, wa
                 return None
             _check(rc, "ofl_warp_bwd_grad_x16")
         if want_src:
-            ws = torch.empty(int(lib.ofl_splat_tiled_workspace_ints(n, h, w)), dtype=torch.int32, device=dev)
-            accum = _fallback_accum(lib, n, c, 0, h, w, dev)
-            gs = torch.empty((n, c, h, w), dtype=dt, device=dev)
-            rc = lib.ofl_splat_sum_x16(_ptr(f), fbs, -float(flow_sign), _ptr(g), c * h * w, float(g_scale), _ptr(gs), _ptr(ws), ws.numel(),
-                                       _ptr(accum), n, c, h, w, _X16_DTYPES[dt], _stream(dev))
-            if rc in (-4, -2):
+            gs = _splat_sum_x16(lib, dev, f, fbs, g, flow_sign=-float(flow_sign), data_sign=float(g_scale))
+            if gs is None:
                 return None
-            _check(rc, "ofl_splat_sum_x16")
-            if collect_splat_stats:
-                global _last_splat_stats
-                _last_splat_stats = ws[:8].clone()
+    return gs, gf
+
+
+def _splat_sum_x16(lib, dev, f, fbs, g, *, flow_sign, data_sign):
+    """ofl_splat_sum_x16 of the contiguous 16-bit planes g [N,C,H,W] along flow_sign * f (staged by `_planes`), inside `_on(dev)`: the
+    gradient of a 16-bit warp with respect to its source, in g's dtype.  None when the library declines the launch."""
+    n, c, h, w = g.shape
+    ws = torch.empty(int(lib.ofl_splat_tiled_workspace_ints(n, h, w)), dtype=torch.int32, device=dev)
+    accum = _fallback_accum(lib, n, c, 0, h, w, dev)
+    gs = torch.empty((n, c, h, w), dtype=g.dtype, device=dev)
+    rc = lib.ofl_splat_sum_x16(_ptr(f), fbs, float(flow_sign), _ptr(g), c * h * w, float(data_sign), _ptr(gs), _ptr(ws), ws.numel(),
+                               _ptr(accum), n, c, h, w, _X16_DTYPES[g.dtype], _stream(dev))
+    if rc in (-4, -2):
+        return None
+    _check(rc, "ofl_splat_sum_x16")
+    if collect_splat_stats:
+        global _last_splat_stats
+        _last_splat_stats = ws[:8].clone()
+    return gs
+
+
+def _nhwc_grad_kind(src: torch.Tensor, grad_out: torch.Tensor):
+    """The `dtype` argument of ofl_warp_bwd_grad_nhwc for a saved source and an upstream gradient that the channels_last backward reads
+    as they are stored, else None: both of one `_nhwc_kind` (channels_last-dense, aligned, one dtype), one shape, one device.  Pure: no
+    device needed."""
+    kind = _nhwc_kind(src)
+    if kind is None or _nhwc_kind(grad_out) != kind or src.shape != grad_out.shape or src.device != grad_out.device:
+        return None
+    return kind
+
+
+def _transpose(t: torch.Tensor, to_planes: bool) -> torch.Tensor:
+    lib, dev = load_library(), t.device
+    if dev.type != 'cuda' or t.dim() != 4 or t.element_size() not in (2, 4) or t.numel() == 0:
+        raise ValueError("oflibpytorch_amd: the layout copies take a non-empty 4-D device tensor of 2- or 4-byte elements")
+    fmt_in, fmt_out = (torch.channels_last, torch.contiguous_format) if to_planes else (torch.contiguous_format, torch.channels_last)
+    if not t.is_contiguous(memory_format=fmt_in):
+        raise ValueError("oflibpytorch_amd: the operand is not dense in the layout this copy reads")
+    n, c, h, w = t.shape
+    with _on(dev):
+        out = torch.empty((n, c, h, w), dtype=t.dtype, device=dev, memory_format=fmt_out)
+        fn, what = (lib.ofl_nhwc_to_planes, "ofl_nhwc_to_planes") if to_planes else (lib.ofl_planes_to_nhwc, "ofl_planes_to_nhwc")
+        _check(fn(_ptr(t), _ptr(out), n, c, h, w, t.element_size(), _stream(dev)), what)
+    return out
+
+
+def nhwc_to_planes(t: torch.Tensor) -> torch.Tensor:
+    """ofl_nhwc_to_planes: the bits of a channels_last-dense device tensor [N,C,H,W] (2- or 4-byte elements, C % 4 == 0, aligned as
+    `_nhwc_kind` asks) as a default-contiguous tensor -- `t.contiguous()` by the library's LDS-tiled transpose.  Raises where the
+    library declines."""
+    return _transpose(t.detach(), True)
+
+
+def planes_to_nhwc(t: torch.Tensor) -> torch.Tensor:
+    """ofl_planes_to_nhwc: the bits of a default-contiguous device tensor [N,C,H,W] as a channels_last-dense one --
+    `t.contiguous(memory_format=torch.channels_last)` by the library's LDS-tiled transpose."""
+    return _transpose(t.detach(), False)
+
+
+def warp_bwd_grad_nhwc(flow, src, grad_out, *, flow_sign=1.0, g_scale=1.0, want_src=True, want_flow=True):
+    """Backward of `_warp_bwd_nhwc` from the channels_last source and upstream gradient as they are stored (`_nhwc_grad_kind`):
+    (grad_src channels_last in the source's dtype | None, grad_flow fp32 [N,2,H,W] | None), bit-identical to `warp_bwd_grad` /
+    `warp_bwd_grad_x16` on `.contiguous()` copies.  The flow gradient is one ofl_warp_bwd_grad_nhwc launch; the source gradient is the
+    planar routes' gather splat between the library's two layout copies (ofl_nhwc_to_planes of the upstream gradient,
+    ofl_planes_to_nhwc of the result; an N-H-W-C gather splat: DESIGN.md section 8) and never reads the source.  None when the call
+    is not of this kind (a planar or strided gradient, another dtype, a source broadcast over the batch, a frame the gather splat does
+    not take) or the library declines a launch; nothing observable has happened then and the caller takes the planar route."""
+    if not (want_src or want_flow) or src.device.type != 'cuda':
+        return None
+    kind = _nhwc_grad_kind(src, grad_out)
+    n, c, h, w = grad_out.shape if grad_out.dim() == 4 else (0, 0, 0, 0)
+    if kind is None or flow.dim() != 4 or flow.shape[0] not in (1, n) or tuple(flow.shape[1:]) != (2, h, w):
+        return None
+    x16 = src.dtype in _X16_DTYPES
+    if want_src and (w < 4 or h * w >= (1 << 24) or h >= 32760 or w >= 32760):
+        return None                         # frames the gather splat does not take: the planar route's atomics kernel does
+    lib, dev = load_library(), src.device
+    with _on(dev):
+        f, fbs = _planes(flow.detach(), dev, torch.float32, n, "flow")
+        s, g = src.detach(), grad_out.detach()
+        gs = gf = None
+        if want_src:
+            gp = torch.empty((n, c, h, w), dtype=g.dtype, device=dev)
+            rc = lib.ofl_nhwc_to_planes(_ptr(g), _ptr(gp), n, c, h, w, g.element_size(), _stream(dev))
+            if rc == -4:
+                return None
+            _check(rc, "ofl_nhwc_to_planes")
+            if x16:
+                full = _splat_sum_x16(lib, dev, f, fbs, gp, flow_sign=-float(flow_sign), data_sign=float(g_scale))
+            else:
+                full = splat_sum(f if fbs != 0 or n == 1 else f.expand(n, -1, -1, -1), gp, flow_sign=-float(flow_sign), data_sign=float(g_scale))
+            if full is None:
+                return None
+            del gp                          # (the planar gradient's block is free again before the result is allocated)
+            gs = torch.empty((n, c, h, w), dtype=src.dtype, device=dev, memory_format=torch.channels_last)
+            rc = lib.ofl_planes_to_nhwc(_ptr(full), _ptr(gs), n, c, h, w, full.element_size(), _stream(dev))
+            if rc == -4:
+                return None
+            _check(rc, "ofl_planes_to_nhwc")
+            del full
+        if want_flow:
+            gf = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+            rc = lib.ofl_warp_bwd_grad_nhwc(_ptr(f), fbs, float(flow_sign), _ptr(s), c * h * w, _ptr(g), float(g_scale), _ptr(gf),
+                                            n, c, h, w, kind, _stream(dev))
+            if rc == -4:
+                return None
+            _check(rc, "ofl_warp_bwd_grad_nhwc")
     return gs, gf
 
 

@@ -210,7 +210,216 @@ int nhwc_launch(NhwcParams& p, int32_t n, hipStream_t st) {
     return (int)hipGetLastError();
 }
 
+// ---- ofl_warp_bwd_grad_nhwc: the gradient of that warp with respect to its FLOW, from the saved source and the upstream gradient as stored ----
+// One pixel per lane; the channels of the pixel and of each of its four taps are contiguous runs, walked in chunks of V (one 16-byte load of
+// the upstream gradient and up to four of the taps per chunk).  The sums are warp_grad_kernel's (ofl_aux_kernels.hip): ONE chain per pixel
+// over the channels 0 .. C-1, the eight updates per channel in that kernel's order and association, then the same chain rule -- so the
+// result is bit-identical to the planar routes' (warp_grad_kernel, warp_grad_flow_x16_kernel, the staged GRAD kernels).  No LDS, no atomics.
+struct NhwcGradParams {
+    const float* flow; int64_t flow_bs;                  // [*, 2, H, W] fp32 planes
+    const void* src; int64_t src_bs;                     // [*, H, W, C]
+    const void* gout;                                    // [N, H, W, C]
+    float* gflow;                                        // [N, 2, H, W] fp32 planes
+    int32_t c, h, w;
+    float flow_sign, g_scale, wm1, hm1, half_wm1, half_hm1;
+};
+
+template <typename T, int V>
+__global__ __launch_bounds__(kThreads) void warp_grad_flow_nhwc_kernel(const NhwcGradParams p) {
+    const int w = p.w, h = p.h;
+    const int64_t hw = (int64_t)h * w;
+    const int64_t pix = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (pix >= hw) return;
+    const int64_t n = blockIdx.y;
+    const int y = (int)(pix / w), x = (int)(pix - (int64_t)y * w);
+    const float* __restrict__ fu = p.flow + n * p.flow_bs;
+    const T* __restrict__ sb = static_cast<const T*>(p.src) + n * p.src_bs;
+    const T* __restrict__ gp = static_cast<const T*>(p.gout) + (n * hw + pix) * p.c;
+
+    const float sx = unnormalise((float)x - p.flow_sign * fu[pix], p.wm1, p.half_wm1);
+    const float sy = unnormalise((float)y - p.flow_sign * fu[hw + pix], p.hm1, p.half_hm1);
+    // the four taps: fractions, validity, offsets clamped into the frame (make_taps of ofl_aux_kernels.hip)
+    const float x_w = floorf(sx), y_n = floorf(sy), x_e = x_w + 1.0f, y_s = y_n + 1.0f;
+    const float ww = sx - x_w, e = 1.0f - ww, nn = sy - y_n, s = 1.0f - nn;
+    const bool x0ok = (x_w > -1.0f) && (x_w < (float)w), x1ok = (x_e > -1.0f) && (x_e < (float)w);
+    const bool y0ok = (y_n > -1.0f) && (y_n < (float)h), y1ok = (y_s > -1.0f) && (y_s < (float)h);
+    const int ix0 = x0ok ? (int)x_w : 0, ix1 = x1ok ? (int)x_e : 0, iy0 = y0ok ? (int)y_n : 0, iy1 = y1ok ? (int)y_s : 0;
+    const T* __restrict__ t_nw = sb + ((int64_t)iy0 * w + ix0) * p.c;
+    const T* __restrict__ t_ne = sb + ((int64_t)iy0 * w + ix1) * p.c;
+    const T* __restrict__ t_sw = sb + ((int64_t)iy1 * w + ix0) * p.c;
+    const T* __restrict__ t_se = sb + ((int64_t)iy1 * w + ix1) * p.c;
+    const bool k_nw = x0ok && y0ok, k_ne = x1ok && y0ok, k_sw = x0ok && y1ok, k_se = x1ok && y1ok;
+
+    float gix = 0.0f, giy = 0.0f;
+    for (int c0 = 0; c0 < p.c; c0 += V) {
+        float gv[V], v_nw[V], v_ne[V], v_sw[V], v_se[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) v_nw[k] = v_ne[k] = v_sw[k] = v_se[k] = 0.0f;
+        Lane<T, V>::load(gp + c0, gv);
+        if (k_nw) Lane<T, V>::load(t_nw + c0, v_nw);
+        if (k_ne) Lane<T, V>::load(t_ne + c0, v_ne);
+        if (k_sw) Lane<T, V>::load(t_sw + c0, v_sw);
+        if (k_se) Lane<T, V>::load(t_se + c0, v_se);
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            const float g = p.g_scale * gv[k];
+            gix -= v_nw[k] * s * g; gix += v_ne[k] * s * g; gix -= v_sw[k] * nn * g; gix += v_se[k] * nn * g;
+            giy -= v_nw[k] * e * g; giy -= v_ne[k] * ww * g; giy += v_sw[k] * e * g; giy += v_se[k] * ww * g;
+        }
+    }
+    float* __restrict__ gf = p.gflow + n * 2 * hw;
+    // grad of the grid (x half_size), of normalise_coords (/ size_m1, * 2), of `grid - flow` (negation)
+    gf[pix] = -p.flow_sign * (((gix * p.half_wm1) / p.wm1) * 2.0f);
+    gf[hw + pix] = -p.flow_sign * (((giy * p.half_hm1) / p.hm1) * 2.0f);
+}
+
+template <typename T, int V>
+int nhwc_grad_launch(const NhwcGradParams& p, int32_t n, hipStream_t st) {
+    const int64_t hw = (int64_t)p.h * p.w;
+    const dim3 grid((unsigned)((hw + kThreads - 1) / kThreads), (unsigned)n);
+    OFL_KLAUNCH((warp_grad_flow_nhwc_kernel<T, V>), grid, dim3(kThreads), 0, st, p);
+    return (int)hipGetLastError();
+}
+
+// ---- ofl_nhwc_to_planes / ofl_planes_to_nhwc: bit copies between [N, H, W, C] and [N, C, H, W] through an LDS tile ----
+// A block moves a tile of TP pixels x TC channels of one image (TC elements = 128 bytes of a pixel: whole cache lines on the N-H-W-C
+// side).  LDS holds it channel-major, tile[ch][px] with a pitch of TP + 1 elements.  N-H-W-C side: item i of the tile is V consecutive
+// channels (one 16-byte access, 8 bytes with 4 16-bit elements) of pixel i / (TC / V), so the lanes of a pixel cover its 128 bytes and
+// consecutive pixels follow; its V elements go to / come from V rows of the tile at one column -- with the odd pitch the 32 lanes of an
+// LDS group (TC / V chunks x a few pixels) fall on distinct banks with 4-byte elements and at worst two to a bank with 2-byte ones.
+// Plane side: consecutive lanes take consecutive pixels of one channel (coalesced; element-sized accesses, as a plane's base is only
+// element-aligned when H * W is odd), consecutive columns of one tile row in LDS.  Tiles at the end of the pixels or of the channels
+// are cut by the bounds tests; C is a multiple of V, so a chunk is inside or outside as a whole.
+template <typename E> struct TileShape;
+template <> struct TileShape<uint32_t> { static constexpr int TP = 64, TC = 32; };
+template <> struct TileShape<uint16_t> { static constexpr int TP = 128, TC = 64; };
+
+template <typename E, int V> struct EVec {
+    typedef E vec __attribute__((ext_vector_type(V), aligned(sizeof(E) == 4 ? 16 : 8)));
+};
+
+struct TransposeParams {
+    const void* src; void* dst;
+    int64_t hw; int32_t c;
+};
+
+// TO_PLANES: src [N, H*W, C] -> dst [N, C, H*W]; else src [N, C, H*W] -> dst [N, H*W, C].  grid (pixel tiles, channel tiles, N)
+template <typename E, int V, bool TO_PLANES>
+__global__ __launch_bounds__(kThreads) void nhwc_transpose_kernel(const TransposeParams p) {
+    constexpr int TP = TileShape<E>::TP, TC = TileShape<E>::TC, PITCH = TP + 1, CPT = TC / V;
+    typedef typename EVec<E, V>::vec vec;
+    __shared__ E tile[TC * PITCH];
+    const int64_t hw = p.hw, C = p.c;
+    const int64_t p0 = (int64_t)blockIdx.x * TP;
+    const int c0 = (int)blockIdx.y * TC;
+    const int64_t img = (int64_t)blockIdx.z * hw * C;
+    const E* __restrict__ src = static_cast<const E*>(p.src) + img;
+    E* __restrict__ dst = static_cast<E*>(p.dst) + img;
+    const int np = (int)(hw - p0 < TP ? hw - p0 : TP);       // pixels and channels of this tile
+    const int nc = (int)(C - c0 < TC ? C - c0 : TC);
+    if (TO_PLANES) {
+#pragma unroll
+        for (int i = threadIdx.x; i < TP * CPT; i += kThreads) {
+            const int px = i / CPT, ch = (i % CPT) * V;
+            if (px < np && ch < nc) {
+                const vec v = *reinterpret_cast<const vec*>(src + (p0 + px) * C + c0 + ch);
+#pragma unroll
+                for (int k = 0; k < V; ++k) tile[(ch + k) * PITCH + px] = v[k];
+            }
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int j = threadIdx.x; j < TP * TC; j += kThreads) {
+            const int ch = j / TP, px = j % TP;
+            if (px < np && ch < nc) dst[(int64_t)(c0 + ch) * hw + p0 + px] = tile[ch * PITCH + px];
+        }
+    } else {
+#pragma unroll 4
+        for (int j = threadIdx.x; j < TP * TC; j += kThreads) {
+            const int ch = j / TP, px = j % TP;
+            if (px < np && ch < nc) tile[ch * PITCH + px] = src[(int64_t)(c0 + ch) * hw + p0 + px];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = threadIdx.x; i < TP * CPT; i += kThreads) {
+            const int px = i / CPT, ch = (i % CPT) * V;
+            if (px < np && ch < nc) {
+                vec v;
+#pragma unroll
+                for (int k = 0; k < V; ++k) v[k] = tile[(ch + k) * PITCH + px];
+                *reinterpret_cast<vec*>(dst + (p0 + px) * C + c0 + ch) = v;
+            }
+        }
+    }
+}
+
+template <typename E, int V, bool TO_PLANES>
+int transpose_launch(const TransposeParams& p, int32_t n, hipStream_t st) {
+    constexpr int TP = TileShape<E>::TP, TC = TileShape<E>::TC;
+    const dim3 grid((unsigned)((p.hw + TP - 1) / TP), (unsigned)((p.c + TC - 1) / TC), (unsigned)n);
+    OFL_KLAUNCH((nhwc_transpose_kernel<E, V, TO_PLANES>), grid, dim3(kThreads), 0, st, p);
+    return (int)hipGetLastError();
+}
+
+// `nhwc` is the operand stored [N, H, W, C] (the source of ofl_nhwc_to_planes, the destination of ofl_planes_to_nhwc)
+template <bool TO_PLANES>
+int transpose_entry(const void* src, void* dst, const void* nhwc, const void* planes, int32_t n, int32_t c, int32_t h, int32_t w,
+                    int32_t elem_bytes, void* stream) {
+    if (!src || !dst) return OFL_E_NULL;
+    if (elem_bytes != 2 && elem_bytes != 4) return OFL_E_ARG;
+    if (n < 0 || c < 0 || h < 0 || w < 0) return OFL_E_ARG;
+    if (n < 1 || c < 1 || h < 1 || w < 1 || (int64_t)h * w >= (1ll << 31)) return OFL_E_SHAPE;
+    if ((uintptr_t)planes & (uintptr_t)(elem_bytes - 1)) return OFL_E_ARG;
+    if ((c & 3) != 0) return OFL_E_UNSUPPORTED;
+    if ((uintptr_t)nhwc & (uintptr_t)(elem_bytes == 4 ? 15 : 7)) return OFL_E_UNSUPPORTED;
+    if (n > 65535 || c > 65535 * 32) return OFL_E_UNSUPPORTED;                   // images and channel tiles on the grid's y and z axes
+    const double bytes = (double)n * c * h * w * elem_bytes;                   // the two operands must not overlap
+    const uintptr_t a = (uintptr_t)src, b = (uintptr_t)dst;
+    if ((a <= b && (double)(b - a) < bytes) || (b < a && (double)(a - b) < bytes)) return OFL_E_ARG;
+    TransposeParams p;
+    p.src = src; p.dst = dst; p.hw = (int64_t)h * w; p.c = c;
+    hipStream_t st = (hipStream_t)stream;
+    if (elem_bytes == 4) return transpose_launch<uint32_t, 4, TO_PLANES>(p, n, st);
+    return (c & 7) == 0 ? transpose_launch<uint16_t, 8, TO_PLANES>(p, n, st) : transpose_launch<uint16_t, 4, TO_PLANES>(p, n, st);
+}
+
 }  // namespace
+
+extern "C" __attribute__((visibility("default"))) int ofl_warp_bwd_grad_nhwc(
+    const float* flow, int64_t flow_bs, float flow_sign, const void* src, int64_t src_bs, const void* grad_out, float g_scale,
+    float* grad_flow, int32_t n, int32_t c, int32_t h, int32_t w, int32_t dtype, void* stream) {
+    if (!flow || !src || !grad_out || !grad_flow) return OFL_E_NULL;
+    if (dtype != OFL_X16_HALF && dtype != OFL_X16_BFLOAT && dtype != OFL_NHWC_F32) return OFL_E_ARG;
+    if (n < 0 || c < 0 || h < 0 || w < 0 || flow_bs < 0 || src_bs < 0) return OFL_E_ARG;
+    if (!(flow_sign == 1.0f || flow_sign == -1.0f)) return OFL_E_ARG;
+    if (n < 1 || c < 1 || h < 1 || w < 1 || (int64_t)h * w >= (1ll << 31)) return OFL_E_SHAPE;
+    // whole chunks of 4 channels, a frame the normalisation is defined on (the divide by size - 1), operands aligned to the chunk's vector
+    if (c < 4 || (c & 3) != 0 || h < 2 || w < 2) return OFL_E_UNSUPPORTED;
+    const uintptr_t align = dtype == OFL_NHWC_F32 ? 16 : 8;
+    if (((uintptr_t)src | (uintptr_t)grad_out) & (align - 1)) return OFL_E_UNSUPPORTED;
+    if (n > 65535) return OFL_E_UNSUPPORTED;                                     // images on the grid's second axis
+    NhwcGradParams p = {};
+    p.flow = flow; p.flow_bs = flow_bs; p.src = src; p.src_bs = src_bs; p.gout = grad_out; p.gflow = grad_flow;
+    p.c = c; p.h = h; p.w = w;
+    p.flow_sign = flow_sign; p.g_scale = g_scale;
+    p.wm1 = (float)(w - 1); p.hm1 = (float)(h - 1);
+    p.half_wm1 = p.wm1 / 2.0f; p.half_hm1 = p.hm1 / 2.0f;
+    hipStream_t st = (hipStream_t)stream;
+    const bool v8 = dtype != OFL_NHWC_F32 && (c & 7) == 0;
+    if (dtype == OFL_NHWC_F32) return nhwc_grad_launch<float, 4>(p, n, st);
+    if (dtype == OFL_X16_HALF) return v8 ? nhwc_grad_launch<half_t, 8>(p, n, st) : nhwc_grad_launch<half_t, 4>(p, n, st);
+    return v8 ? nhwc_grad_launch<bf16_t, 8>(p, n, st) : nhwc_grad_launch<bf16_t, 4>(p, n, st);
+}
+
+extern "C" __attribute__((visibility("default"))) int ofl_nhwc_to_planes(
+    const void* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t elem_bytes, void* stream) {
+    return transpose_entry<true>(src, dst, src, dst, n, c, h, w, elem_bytes, stream);
+}
+
+extern "C" __attribute__((visibility("default"))) int ofl_planes_to_nhwc(
+    const void* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t elem_bytes, void* stream) {
+    return transpose_entry<false>(src, dst, dst, src, n, c, h, w, elem_bytes, stream);
+}
 
 extern "C" __attribute__((visibility("default"))) int ofl_warp_bwd_nhwc(
     const float* flow, int64_t flow_bs, float flow_sign, const void* src, int64_t src_bs,
