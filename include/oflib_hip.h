@@ -760,6 +760,45 @@ int ofl_mesh_points(const float* flow, int64_t flow_bs, float flow_sign, const u
                     int64_t pts_bs, int32_t* workspace, int32_t* list, int64_t list_ints, double* vecs, uint8_t* inside, int32_t nf,
                     int32_t m, int32_t h, int32_t w, void* stream);
 
+/*
+ * The dataset loaders: Flow.from_kitti / from_sintel, load_kitti / load_sintel / load_sintel_mask (reference
+ * flow_class.py:330-374, utils.py:810-875).
+ *
+ * HOST side (ofl_png_host.cpp: plain C++, HOST pointers, no HIP call -- the one exception to "every pointer is a device pointer").  The
+ * binding parses the PNG chunks and inflates the IDAT stream; these two undo what is sequential per byte lane.  Every length comes from
+ * the caller and nothing is read or written beyond it, whatever the bytes say.
+ *
+ * ofl_png_unfilter: `inflated` = height scanlines of one filter byte (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth) + row_bytes samples, with
+ *   row_bytes = ceil(width * channels * bit_depth / 8) and channels 1 / 3 / 1 / 2 / 4 for colour type 0 / 2 / 3 / 4 / 6; `out` = the
+ *   height * row_bytes unfiltered bytes (samples as the file stores them: 16-bit ones big-endian).  Non-interlaced images only.
+ *   OFL_E_SHAPE: width or height outside 1 .. 2^24, inflated_len != height * (row_bytes + 1), out_len != height * row_bytes;
+ *   OFL_E_ARG: a colour type / bit depth pair PNG does not define, a filter byte above 4 (nothing of `out` is meaningful then).
+ * ofl_png_grey8: the 8-bit grey value cv2.imread(path, 0) gives for every pixel of an unfiltered image: grey 8 bits as stored, 1 / 2 / 4
+ *   bits scaled by 255 / 85 / 17, 16 bits the high byte; 8-bit R G B (colour type 2, 6: alpha ignored; 3: the palette entry, `palette`
+ *   = palette_entries * 3 bytes) as (4899 R + 9617 G + 1868 B + 8192) >> 14.  (cvtColor's weights; not verified against cv2.imread for
+ *   colour / palette images)  grey = height * width bytes.  OFL_E_UNSUPPORTED: grey with
+ *   alpha, 16-bit colour; OFL_E_ARG: a palette index beyond palette_entries, an undefined pair; OFL_E_SHAPE: lengths as above.
+ *
+ * DEVICE side (ofl_loaders.hip; device pointers as everywhere else).  One lane decodes 4 consecutive pixels of the dense image; both
+ * kernels also form the image's flag word (OFL_FLAG_*; flags int32[n], zeroed in-stream) exactly as ofl_flow_flags_f32 would for the
+ * vectors and mask they write, so that nothing has to read them again.  n <= 65535, h * w < 2^31.
+ *
+ * ofl_decode_kitti: raw = n images of h * w * 3 big-endian 16-bit samples R G B (raw_bs BYTES between images, >= 6 h w), any alignment
+ *   (16-byte / 8-byte loads where an image's first byte is 8-byte aligned).  vecs fp32 [n,2,h,w]: u = (R - 32768) / 64,
+ *   v = (G - 32768) / 64 (exact in fp32); mask (optional) uint8 [n,h,w] = B > 0.  Without `mask` the flags are those of an all-True mask.
+ * ofl_decode_flo: raw = n images of h * w interleaved (u, v) fp32 pairs (raw_bs FLOATS between images, >= 2 h w; 4-byte aligned, else
+ *   OFL_E_ARG), copied to the planes of vecs bit for bit; grey (optional) uint8 [n,h,w] (grey_bs bytes between images) and mask uint8
+ *   [n,h,w] = grey == 0 -- both or neither, else OFL_E_ARG.
+ */
+int ofl_png_unfilter(const uint8_t* inflated, int64_t inflated_len, int32_t width, int32_t height, int32_t bit_depth,
+                     int32_t colour_type, uint8_t* out, int64_t out_len);
+int ofl_png_grey8(const uint8_t* raw, int64_t raw_len, int32_t width, int32_t height, int32_t bit_depth, int32_t colour_type,
+                  const uint8_t* palette, int32_t palette_entries, uint8_t* grey, int64_t grey_len);
+int ofl_decode_kitti(const uint8_t* raw, int64_t raw_bs, float* vecs, uint8_t* mask, int32_t* flags, int32_t n, int32_t h, int32_t w,
+                     void* stream);
+int ofl_decode_flo(const float* raw, int64_t raw_bs, const uint8_t* grey, int64_t grey_bs, float* vecs, uint8_t* mask, int32_t* flags,
+                   int32_t n, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,8 +32,10 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_arrows_workspace_ints", "ofl_arrows_scale_f32", "ofl_arrows_plan", "ofl_arrows_u8",
             "ofl_mesh_workspace_ints", "ofl_mesh_plan", "ofl_mesh_apply", "ofl_mesh_points",
             "ofl_warp_bwd_x16", "ofl_warp_bwd_grad_x16", "ofl_splat_sum_x16", "ofl_warp_bwd_nhwc",
-            "ofl_warp_bwd_grad_nhwc", "ofl_nhwc_to_planes", "ofl_planes_to_nhwc")
+            "ofl_warp_bwd_grad_nhwc", "ofl_nhwc_to_planes", "ofl_planes_to_nhwc",
+            "ofl_png_unfilter", "ofl_png_grey8", "ofl_decode_kitti", "ofl_decode_flo")
 _lib = None
+_load_lock = threading.RLock()
 
 
 class NativeUnavailable(RuntimeError):
@@ -42,6 +44,15 @@ class NativeUnavailable(RuntimeError):
 
 def load_library(path: str = None):
     """dlopen libofl_hip.so and declare the C ABI.  Never touches the GPU (usable in CPU-only checks)."""
+    if _lib is not None and path is None:
+        return _lib
+    # one thread at a time: the first call may rebuild the library (a dozen compiler processes, one link into a file named after the
+    # process), and callers can be the workers of a thread pool (the dataset loaders' batches)
+    with _load_lock:
+        return _load_library_locked(path)
+
+
+def _load_library_locked(path: str = None):
     global _lib
     if _lib is not None and path is None:
         return _lib
@@ -126,6 +137,10 @@ def load_library(path: str = None):
     lib.ofl_warp_bwd_grad_nhwc.argtypes = [p, i64, f32, p, i64, p, f32, p, i32, i32, i32, i32, i32, p]
     lib.ofl_nhwc_to_planes.argtypes = [p, p, i32, i32, i32, i32, i32, p]
     lib.ofl_planes_to_nhwc.argtypes = [p, p, i32, i32, i32, i32, i32, p]
+    lib.ofl_png_unfilter.argtypes = [p, i64, i32, i32, i32, i32, p, i64]
+    lib.ofl_png_grey8.argtypes = [p, i64, i32, i32, i32, i32, p, i32, p, i64]
+    lib.ofl_decode_kitti.argtypes = [p, i64, p, p, p, i32, i32, i32, p]
+    lib.ofl_decode_flo.argtypes = [p, i64, p, i64, p, p, p, i32, i32, i32, p]
     for name in _SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     lib.ofl_arrows_workspace_ints.restype = ctypes.c_int64
@@ -1485,3 +1500,71 @@ def splat_fwd_win(flow, data, window, *, weight_mask=None, chan_mask_a=None, cha
             global _last_splat_stats
             _last_splat_stats = ws[:8].clone()
     return dst, valid
+
+
+# ------------------------------------------------------------------------------------------------
+# dataset loaders: host unfilter / grey rule (no GPU involved), device decode kernels
+# ------------------------------------------------------------------------------------------------
+def png_unfilter(inflated: bytes, width: int, height: int, bit_depth: int, colour_type: int, out: np.ndarray = None, lib=None):
+    """ofl_png_unfilter on HOST memory: the inflated IDAT stream -> the unfiltered bytes, uint8 [height * row_bytes] (into `out`, a
+    contiguous uint8 array of exactly that size, if given).  Returns (status, array): the caller words the error."""
+    lib = load_library() if lib is None else lib
+    channels = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}.get(colour_type, 0)
+    size = height * ((width * channels * bit_depth + 7) // 8) if (width > 0 and height > 0) else 0
+    if out is None:
+        out = np.empty(size, dtype=np.uint8)
+    if out.dtype != np.uint8 or not out.flags['C_CONTIGUOUS']:
+        raise ValueError("oflibpytorch_amd: png_unfilter needs a contiguous uint8 output")
+    src = np.frombuffer(inflated, dtype=np.uint8)
+    rc = lib.ofl_png_unfilter(ctypes.c_void_p(src.ctypes.data), src.size, width, height, bit_depth, colour_type,
+                              ctypes.c_void_p(out.ctypes.data), out.size)
+    return rc, out
+
+
+def png_grey8(raw: np.ndarray, width: int, height: int, bit_depth: int, colour_type: int, palette: bytes = None, lib=None):
+    """ofl_png_grey8 on HOST memory: unfiltered bytes -> (status, uint8 [height, width]) the grey value cv2.imread(path, 0) gives."""
+    lib = load_library() if lib is None else lib
+    raw = np.ascontiguousarray(raw, dtype=np.uint8).reshape(-1)
+    grey = np.empty((max(height, 0), max(width, 0)), dtype=np.uint8)
+    pal = None if palette is None else np.frombuffer(palette, dtype=np.uint8)
+    rc = lib.ofl_png_grey8(ctypes.c_void_p(raw.ctypes.data), raw.size, width, height, bit_depth, colour_type,
+                           ctypes.c_void_p(0 if pal is None else pal.ctypes.data), 0 if pal is None else pal.size // 3,
+                           ctypes.c_void_p(grey.ctypes.data), grey.size)
+    return rc, grey
+
+
+def decode_kitti(raw: torch.Tensor, h: int, w: int, want_mask: bool = True):
+    """ofl_decode_kitti: raw uint8 [N, >= 6 h w] (rows of one image each: big-endian 16-bit R G B, last dimension contiguous; any
+    storage offset) -> (vecs fp32 [N,2,H,W], mask bool [N,H,W] or None, flag words int32 [N]) on the HIP device, one launch."""
+    lib, dev = load_library(), device(raw)
+    if raw.dtype != torch.uint8 or raw.dim() != 2 or raw.shape[1] < 6 * h * w or (raw.shape[1] > 1 and raw.stride(1) != 1):
+        raise ValueError("oflibpytorch_amd: decode_kitti needs uint8 [N, 6 * H * W] with contiguous rows")
+    n = raw.shape[0]
+    with _on(dev):
+        raw = raw.to(dev)
+        vecs = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+        mask = torch.empty((n, h, w), dtype=torch.bool, device=dev) if want_mask else None
+        flags = torch.empty(n, dtype=torch.int32, device=dev)
+        _check(lib.ofl_decode_kitti(_ptr(raw), raw.stride(0) if n > 1 else raw.shape[1], _ptr(vecs), _ptr(mask), _ptr(flags), n, h, w,
+                                    _stream(dev)), "ofl_decode_kitti")
+    return vecs, mask, flags
+
+
+def decode_flo(raw: torch.Tensor, grey: torch.Tensor = None):
+    """ofl_decode_flo: raw fp32 [N,H,W,2] (an image's pairs dense; any 4-byte aligned storage offset), grey uint8 [N,H,W] or None ->
+    (vecs fp32 [N,2,H,W] with raw's bit patterns, mask bool [N,H,W] = grey == 0 or None, flag words int32 [N]), one launch."""
+    lib, dev = load_library(), device(raw, grey)
+    if raw.dtype != torch.float32 or raw.dim() != 4 or raw.shape[3] != 2 or not raw[0].is_contiguous():
+        raise ValueError("oflibpytorch_amd: decode_flo needs fp32 [N, H, W, 2] with dense images")
+    n, h, w, _ = raw.shape
+    if grey is not None and (grey.dtype != torch.uint8 or tuple(grey.shape) != (n, h, w)):
+        raise ValueError("oflibpytorch_amd: decode_flo needs a uint8 [N, H, W] grey plane")
+    with _on(dev):
+        raw = raw.to(dev)
+        g = None if grey is None else grey.to(dev).contiguous()
+        vecs = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+        mask = None if g is None else torch.empty((n, h, w), dtype=torch.bool, device=dev)
+        flags = torch.empty(n, dtype=torch.int32, device=dev)
+        _check(lib.ofl_decode_flo(_ptr(raw), raw.stride(0) if n > 1 else 2 * h * w, _ptr(g), h * w, _ptr(vecs), _ptr(mask), _ptr(flags),
+                                  n, h, w, _stream(dev)), "ofl_decode_flo")
+    return vecs, mask, flags

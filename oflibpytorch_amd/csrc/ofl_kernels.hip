@@ -62,6 +62,8 @@ __device__ __forceinline__ float apply_round(float r, int mode) {
     return r;
 }
 
+// (ofl_loaders.hip keeps a copy of this function and of the wave / block OR below for its decode kernels, which emit the same word:
+// a change to a flag bit is made in both; tests/test_gpu_loaders.py compares their words)
 __device__ __forceinline__ int flag_bits(float u, float v, bool valid) {
     int f = 0;
     const bool nf = !(isfinite(u) && isfinite(v));

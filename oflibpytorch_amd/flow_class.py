@@ -444,6 +444,34 @@ class Flow(object):
         on = device if (device is not None and device.type == 'cuda') else None
         return cls(from_transforms(transform_list, shape, ref, padding, _device=on), ref, mask, device)
 
+    @classmethod
+    def from_kitti(cls, path, load_valid: bool = None, device=None) -> FlowAlias:
+        """flow_class.py:330-355: the flow of a KITTI ``uint16`` .png file as an 's' flow, the valid pixels as its mask unless
+        `load_valid` is False.  The file's raw samples are decoded on the HIP device by one kernel that also leaves the flag word,
+        so no validation pass follows.  Extension: `path` may be a list / tuple of paths of equally sized
+        frames, which come back as one N-batch flow from one launch."""
+        load_valid = True if load_valid is None else load_valid
+        if not isinstance(load_valid, bool):
+            raise TypeError("Error loading flow from KITTI data: Load_valid needs to be boolean")
+        device = get_valid_device(device) if device is not None else torch.device('cpu')
+        from . import _loaders
+        vecs, mask, flags, _ = _loaders.kitti(path, load_valid)
+        return cls._wrap(vecs, 's', mask, device, flags=flags, fresh=True)
+
+    @classmethod
+    def from_sintel(cls, path, inv_path=None, device=None) -> FlowAlias:
+        """flow_class.py:357-374: the flow of a Sintel .flo file as an 's' flow; with `inv_path` the mask is False where that
+        .png's grey value is non-zero.  Decoded as `from_kitti`; NaN / Inf in the file raise the constructor's ValueError.
+        Extension: `path` (and `inv_path`) may be lists / tuples of equal length."""
+        device = get_valid_device(device) if device is not None else torch.device('cpu')
+        from . import _loaders
+        vecs, mask, flags, _, mask_error = _loaders.sintel(path, inv_path)
+        flow = cls._wrap(vecs, 's', mask, device, flags=flags, fresh=True)
+        flow._require_finite("Error setting flow vectors: ")
+        if mask_error is not None:                # (after the vectors' own error, as in the constructor)
+            raise ValueError(mask_error)
+        return flow
+
     # ------------------------------------------------------------------------------------------
     # copies, indexing (flow_class.py:376-448)
     # ------------------------------------------------------------------------------------------

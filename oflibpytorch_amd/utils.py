@@ -414,6 +414,33 @@ def from_transforms(transform_list: list, shape, ref: str = None, padding: list 
 
 
 # ------------------------------------------------------------------------------------------------
+# dataset files (utils.py:810-875): parsed without OpenCV, decoded on the HIP device (_loaders.py)
+# ------------------------------------------------------------------------------------------------
+def load_kitti(path) -> torch.Tensor:
+    """KITTI ``uint16`` .png flow file -> float32 CPU tensor 3-H-W: u, v and the valid pixels as 0 / 1 (utils.py:810-829).
+    Extension: a list / tuple of paths of equally sized frames gives N-3-H-W."""
+    from . import _loaders
+    vecs, mask, _, single = _loaders.kitti(path, True)
+    out = torch.cat((vecs, mask.unsqueeze(1).to(torch.float32)), dim=1).cpu()
+    return out[0] if single else out
+
+
+def load_sintel(path) -> torch.Tensor:
+    """Sintel .flo file -> float32 CPU tensor 2-H-W (utils.py:832-855; the file's length is checked against its header).
+    Extension: a list / tuple of paths of equally sized frames gives N-2-H-W."""
+    from . import _loaders
+    vecs = _loaders.sintel(path)[0].cpu()
+    return vecs[0] if not isinstance(path, (list, tuple)) else vecs
+
+
+def load_sintel_mask(path) -> torch.Tensor:
+    """Sintel invalid-pixel .png -> bool CPU tensor H-W, True = valid: the pixels whose grey value, as ``cv2.imread(path, 0)``
+    would give it, is zero (utils.py:858-875).  Extension: a list / tuple of paths gives N-H-W."""
+    from . import _loaders
+    return _loaders.sintel_mask(path)
+
+
+# ------------------------------------------------------------------------------------------------
 # hot path
 # ------------------------------------------------------------------------------------------------
 def normalise_coords(coords: torch.Tensor, shape: Union[tuple, list]) -> torch.Tensor:
