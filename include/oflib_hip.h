@@ -294,7 +294,9 @@ int ofl_splat_tiled_win_f32(const float* flow, int64_t flow_bs, float flow_sign,
 /*
  * The weighted sums of a forward splat WITHOUT the division by the density:
  *   dst[n,c,q] = sum over source pixels i and corners k that land on q of  w_ik * data_sign * data[n,c,i]
- * with the end points and weights of ofl_splat_tiled_f32 (every pixel contributes: no weight mask, no occlusion rule).
+ * with the weights of ofl_splat_tiled_f32 (every pixel contributes: no weight mask, no occlusion rule) at the end points
+ * unnormalise(grid + flow_sign * flow) -- the float32 sample positions of ofl_warp_bwd_f32, through normalise_coords and the
+ * grid sampler's un-normalise on every axis longer than 1, so that the weights are the forward warp's bit for bit.
  * This is the transpose of the backward warp: with data = the upstream gradient and flow_sign = MINUS the warp's
  * flow_sign it is the gradient of ofl_warp_bwd_f32 with respect to its source (ATen: the grad_input scatter of
  * grid_sampler_2d_backward) -- one gather launch instead of twelve global float atomics per pixel (B=16 1080p C=3:

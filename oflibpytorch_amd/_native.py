@@ -8,6 +8,7 @@ accepts CPU tensors; the arithmetic still runs in the HIP kernels) and results a
 HIP device -- callers move them where the reference would have put them.
 """
 import ctypes
+import math
 import os
 import threading
 import time
@@ -919,7 +920,10 @@ def warp_bwd_grad(flow, src, grad_out, *, flow_sign=1.0, g_scale=1.0, want_src=T
         if want_src:
             # grad wrt the source = the un-normalised forward splat of the upstream gradient along the negated flow: the gather
             # kernels instead of 4 * C global float atomics per pixel (ofl_splat_sum_f32; B=16 1080p C=3: 7.1 -> 1.0 ms)
-            full = splat_sum(f if fbs != 0 or n == 1 else f.expand(n, -1, -1, -1), g, flow_sign=-float(flow_sign), data_sign=float(g_scale))
+            # (the splat takes a sign only: another scale is applied to the gradient first -- g_scale * g, then w * g, as warp_grad_kernel)
+            unit = abs(float(g_scale)) == 1.0
+            full = splat_sum(f if fbs != 0 or n == 1 else f.expand(n, -1, -1, -1), g if unit else g * abs(float(g_scale)),
+                             flow_sign=-float(flow_sign), data_sign=float(g_scale) if unit else math.copysign(1.0, float(g_scale)))
             if full is not None:
                 gs = full.sum(0, keepdim=True) if (ns == 1 and n > 1) else full
         atomics = want_src and gs is None                   # shapes the gather splat does not take (W < 4 ...)

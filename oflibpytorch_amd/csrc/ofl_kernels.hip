@@ -1875,6 +1875,16 @@ inline bool splat_is_lean(const SplatParams& s) {
 #define OFL_SP_RAW(s_) ((s_).raw != 0)          /* (run-time in the lean kernels too: the warp's backward pass -- ofl_splat_sum_f32 -- is a lean call) */
 #define OFL_SP_ROUND(s_) (std::remove_reference<decltype(s_)>::type::kLean ? (int32_t)OFL_ROUND_NONE : (s_).round_mode)
 
+// Raw sums (ofl_splat_sum_f32 / _x16: the gradient of the backward warp with respect to its source): the warp samples at
+// unnormalise(grid - flow) -- its position passes through normalise_coords and the grid sampler's un-normalise, four more float32
+// roundings -- and the gradient's bilinear weights are the forward's, so the end point takes the same chain (bit for bit the position
+// of warp_grad_kernel; without it the weights were off by the position's rounding, ~1e-5 of a pixel at W = 128).  A size-1 axis has
+// no such chain (a division by 0 in the reference): the end point stays.
+__device__ __forceinline__ float sp_warp_position(float p, int size) {
+    const float size_m1 = (float)(size - 1);
+    return size > 1 ? unnormalise(p, size_m1, size_m1 / 2.0f) : p;
+}
+
 // flow window (padded apply): offset of frame pixel (x, y) in a flow-geometry plane (clamped: replicate) and whether it is inside
 template <typename SP>
 __device__ __forceinline__ uint32_t sp_win(const SP& s, int x, int y, bool& inside) {
@@ -1935,6 +1945,7 @@ __device__ __forceinline__ void splat_fwd_tiles(const SplatParams& p) {
             const float u = ld1(fu + fpix), v = ld1(fu + fhw + fpix);
             xv = p.flow_sign * u + (float)x;  // get_flow_endpoints utils.py:1056-1057
             yv = p.flow_sign * v + (float)y;
+            if (p.raw) { xv = sp_warp_position(xv, w); yv = sp_warp_position(yv, h); }
             if (p.occlude) zero = (u < kZeroThr) && (u > -kZeroThr) && (v < kZeroThr) && (v > -kZeroThr);
         } else {
             xv = p.xs[n * p.xy_bs + pix];
@@ -2228,6 +2239,10 @@ __device__ __forceinline__ void sp_finish_src(const SP& s, int sx4, int sy, bool
         }
         const bool wm = ((wm4 >> (8 * k)) & 0xffu) != 0u;
         if (inimg && (sx4 + k < s.w) && wm && !zero) q.on |= 1u << k;
+    }
+    if (OFL_SP_HAS_FLOW(s) && OFL_SP_RAW(s)) {                      // (one uniform test per group: the other splats pay nothing per pixel)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { q.x[k] = sp_warp_position(q.x[k], s.w); q.y[k] = sp_warp_position(q.y[k], s.h); }
     }
 }
 

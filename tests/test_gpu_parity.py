@@ -1231,16 +1231,22 @@ def test_flag_words_or_for_the_sharded_reduce(dev):
 
 def _splat_sum_reference(flow, data, flow_sign, data_sign):
     """ofl_splat_sum_f32 restated with loops (small frames): per corner class, in raster order of the source pixels, then
-    ((c0 + c1) + c2) + c3 -- the order of utils.py:1133-1143 without the division of :1144."""
+    ((c0 + c1) + c2) + c3 -- the order of utils.py:1133-1143 without the division of :1144.  The end point is the backward warp's
+    sample position: grid + flow_sign * flow through normalise_coords and the grid sampler's un-normalise (the weights of the
+    gradient are the forward's)."""
     n, c, h, w = data.shape
     out = np.zeros((n, c, h, w), np.float32)
     f32 = np.float32
+
+    def position(p, size):
+        g = f32(f32(f32(p * f32(2)) / f32(size - 1)) - f32(1))
+        return f32(f32(g + f32(1)) * f32(f32(size - 1) / f32(2)))
     for b in range(n):
         acc = np.zeros((4, c, h, w), np.float32)
         for y in range(h):
             for x in range(w):
-                xv = f32(f32(flow_sign) * flow[b, 0, y, x] + f32(x))
-                yv = f32(f32(flow_sign) * flow[b, 1, y, x] + f32(y))
+                xv = position(f32(f32(flow_sign) * flow[b, 0, y, x] + f32(x)), w)
+                yv = position(f32(f32(flow_sign) * flow[b, 1, y, x] + f32(y)), h)
                 x0, y0 = np.floor(xv), np.floor(yv)
                 for ky in range(2):
                     for kx in range(2):
@@ -1260,7 +1266,8 @@ def _splat_sum_reference(flow, data, flow_sign, data_sign):
 @pytest.mark.parametrize("shape", [(2, 3, 40, 56), (1, 5, 33, 45), (2, 2, 64, 72)])
 def test_splat_sum_is_the_unnormalised_splat_bit_for_bit(shape, dev):
     """ofl_splat_sum_f32 (the gradient of the backward warp wrt its source) against its loop restatement: bit-exact on a
-    fold-free flow, both signs, more than three channels, odd widths."""
+    fold-free flow, both signs, more than three channels, odd widths.  (The restatement's end points are the warp's sample
+    positions since tests/test_gpu_grad_oracle64.py found the weights off by the position's rounding.)"""
     from oflibpytorch_amd import _native
     _native.collect_splat_stats = True
     n, c, h, w = shape
