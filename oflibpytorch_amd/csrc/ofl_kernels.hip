@@ -18,13 +18,14 @@
 
 #pragma clang fp contract(off)
 
-// the four-tile column kernel on 64 x 16 tiles (ofl_warp_wide.hip: this file compiled with OFL_WIDE_TU); `params` = a WarpParams
-int ofl_wide_launch_column(const void* params, int nc, int valid, int add, int rows, void* stream);   // rows: per-row extents (warp_bwd_rows_kernel) where they apply
-int ofl_wide_launch_rows_small(const void* params, int nc, int valid, int add, int tiles, void* stream);   // small plain launches / mode 3: row tables, 1 or 2 tiles per block
+// the kernels on 64 x 16 tiles (ofl_warp_wide.hip: this file compiled with OFL_WIDE_TU); `params` = a WarpParams.  WHICH of them a call
+// runs on is decided by warp_choose() alone: these launch what they are told, `tiles` per block
+int ofl_wide_launch_column(const void* params, int nc, void* stream);          // the four-tile column kernel of a plain warp on the sheared rectangle
+int ofl_wide_launch_rows(const void* params, int nc, int tiles, void* stream);     // the row-table kernel (per-row extents) on fp32 planes: plain and mode 3 at 1 / 2 / OFL_ROWS_T tiles, the other flow-level variants at OFL_ROWS_T
 int ofl_wide_launch_rows_h(const void* params, void* stream);                  // fp16 sources on the row-table kernel
 int ofl_wide_launch_rows_grad(const void* params, int nc, int tiles, void* stream);       // gradient wrt the flow on the row-table kernel
 int ofl_wide_launch_rows_u8(const void* params, int nc, int dst_is_u8, void* stream);         // uint8 images (bytes in; bytes or fp32 out) on the row-table kernel
-int ofl_wide_launch_chan(const void* params, int valid, int rows, void* stream);      // the channel-loop kernel (C >= 4) on 64 x 16 tiles; rows: per-row extents where they apply
+int ofl_wide_launch_chan(const void* params, int rows, void* stream);          // the channel-loop kernel (C >= 4); rows: with per-row extents
 // the warp-path / shear options of ofl_set_option, for the 16-bit launcher (ofl_warp_half.hip: this file compiled with OFL_X16_TU)
 int ofl_warp_path_option(void);
 int ofl_warp_shear_option(void);
@@ -304,10 +305,7 @@ __device__ __forceinline__ f4 rot4(f4 v, int d) { return d == 1 ? (f4){v[1], v[2
 #define OFL_LDS_BYTES 26624
 #endif
 constexpr int kLdsNT = OFL_LDS_NT, kLdsTWQ = OFL_LDS_TWQ, kLdsTH = kLdsNT / kLdsTWQ, kLdsIters = 3;
-#ifndef OFL_WARP_T
-#define OFL_WARP_T 4
-#endif
-constexpr int kLdsT = OFL_WARP_T;    // tiles per block of the column kernel (warp_bwd_lds_column_kernel); 2: the pair kernel only
+constexpr int kLdsT = 4;             // tiles per block of the column kernel (warp_bwd_lds_column_kernel)
 constexpr int kLdsBytes = OFL_LDS_BYTES;   // 6 blocks (12 waves) per CU
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -596,7 +594,7 @@ constexpr int kRowTab = 64;                    // rows of a tile's row table
 #define OFL_ROWS_T 4          // tiles per column of large launches (2 and 3 measured: slower at B = 8 and at B = 64; 6 and 8, with an early exit below the frame: apply level, mode 3 +3 ... 5 % -- the prologue is not what is left)
 #endif
 #ifndef OFL_WARP_CHAN_WIDE_MIN
-#define OFL_WARP_CHAN_WIDE_MIN (2 * 6912u)      // 32 x 16 tiles of the launch from which the channel loop on the RECTANGLE runs on 64 x 16 tiles (with row extents: every size)
+#define OFL_WARP_CHAN_WIDE_MIN (2 * kColumnMinGroups)      // 32 x 16 tiles of the launch from which the channel loop on the RECTANGLE runs on 64 x 16 tiles (with row extents: every size)
 #endif
 #ifndef OFL_ROWS_T1_MAX
 #define OFL_ROWS_T1_MAX 5000u      // 32 x 16 tiles of a launch below which the row-table kernel runs one tile per block (above: two, up to the column threshold); tools/shapes_once.py: 3 600 / 4 096 tiles 3 % better with one, 6 144 tiles 13 % better with two
@@ -3784,6 +3782,164 @@ inline unsigned warp_geometry(WarpParams& p, int tile_w, int tile_h) {
     return (unsigned)(p.per_xcd * kXcds);
 }
 
+// ------------------------------------------------------------------------------------------------
+// the staged backward warp: frame tests, the parameter fill, the path option, and the ONE place that picks a kernel (warp_choose)
+// ------------------------------------------------------------------------------------------------
+// the frames the staged kernels take: at least one whole 4-pixel group per row, 16-bit box coordinates (any width: 16-byte accesses at
+// 4-byte alignment, mask bytes at any alignment), 24-bit pixel offsets
+inline bool warp_frame_staged(int32_t h, int32_t w) { return w >= 4 && h >= 2 && w < 32760 && h < 32760 && (int64_t)h * w < (1ll << 24); }
+// a grid of the smallest tiles (32 x 16) would pass 2^31 blocks
+inline bool warp_tiles_overflow(int32_t n, int32_t h, int32_t w) { return (int64_t)((w + 31) / 32) * ((h + 15) / 16) * n >= (1ll << 31); }
+// blocks of a launch on tile_w x tile_h tiles (warp_geometry's count, without its params): the thresholds below are all counts in the
+// 32-wide geometry, whatever the tile of the translation unit, so that a 16-bit or 64-wide launch changes kernel where the 32-wide one does
+inline unsigned warp_tiles(int32_t n, int32_t h, int32_t w, int tile_w, int tile_h) {
+    const int64_t t = (int64_t)((w + tile_w - 1) / tile_w) * ((h + tile_h - 1) / tile_h) * n;
+    return (unsigned)(((t + kXcds - 1) / kXcds) * kXcds);
+}
+
+// every field zero / null but the frame, the flow operand, neutral signs and the constants the kernels derive from the frame; the entry
+// points set what is theirs on top
+inline void warp_params_init(WarpParams& p, int32_t n, int32_t c, int32_t h, int32_t w, const float* flow, int64_t flow_bs, float flow_sign) {
+    p = WarpParams{};
+    p.flow = flow; p.flow_bs = flow_bs; p.flow_sign = flow_sign;
+    p.n = n; p.c = c; p.h = h; p.w = w;
+    p.a_sign = 1.0f; p.g_sign = 1.0f; p.round_mode = OFL_ROUND_NONE;
+    p.wm1 = (float)(w - 1); p.hm1 = (float)(h - 1);
+    p.half_wm1 = p.wm1 / 2.0f; p.half_hm1 = p.hm1 / 2.0f;
+    p.rcp_wm1 = 1.0f / p.wm1; p.rcp_hm1 = 1.0f / p.hm1;
+    p.lds_bytes = kLdsBytes;
+    p.shear = (ofl_warp_shear_option() && (int64_t)h + 4 * (int64_t)w + 8 < 32760) ? 1 : 0;   // sheared rows stay within 16 bits (|slope| <= 16 rows per chunk column)
+}
+
+// ofl_set_option(OFL_OPT_WARP_PATH, .)
+enum WarpPath : int {
+    kPathAuto = 0,
+    kPathGeneric = 1,        // the generic direct-gather kernel only
+    kPathAuto2 = 2,          // (= auto, but for the small-launch row tables of kPathAuto)
+    kPathPair = 3,           // staged with two tiles per block whatever the launch size (tests)
+    kPathOneTile = 4,        // staged with one tile per block whatever the launch size (tests)
+    kPathChannelGroups = 5,  // auto, but more than 3 channels as separate launches of 3 (tests: the channel-loop kernel against them)
+    kPathRectangle = 6,      // auto, but the sheared rectangle instead of per-row extents (tests, A/B)
+    kPathRowColumns = 7,     // auto, but plain lean launches on four-tile row-table columns whatever the size (tests)
+};
+inline bool path_staged(int path) { return path != kPathGeneric; }
+inline bool path_columns(int path) { return path != kPathPair && path != kPathOneTile; }      // large launches may take four tiles per block
+inline bool path_rows(int path) { return path_columns(path) && path != kPathRectangle; }      // ... and per-row extents (row tables)
+// a launch of the staged kernels (a flow WINDOW is read by the generic kernel only)
+inline bool warp_staged(const WarpParams& p, int path) { return path_staged(path) && warp_frame_staged(p.h, p.w) && p.fw == 0; }
+
+// what a launch of the staged backward warp runs on
+enum WarpFamily : uint8_t {
+    kWarpGeneric,            // not a frame (or path option) of the staged kernels
+    kWarpSplit,              // more than 3 channels and no channel loop: launches of 3 channels, each with a choice of its own
+    kWarpPair,               // warp_bwd_lds_kernel: two tiles per block, the sheared rectangle
+    kWarpColumn,             // warp_bwd_lds_column_kernel: one or kLdsT tiles per block, the sheared rectangle
+    kWarpRows,               // warp_bwd_rows_kernel: 1 / 2 / OFL_ROWS_T tiles per block, per-row extents (64 x 16 tiles)
+    kWarpChan,               // warp_bwd_lds_chan_kernel: all channels in one launch, the sheared rectangle
+    kWarpChanRows,           // ... with per-row extents (64 x 16 tiles)
+};
+struct WarpChoice {
+    WarpFamily family;
+    uint8_t tiles;           // tiles per block
+    bool lean;               // the WarpParamsLean instantiation (rows / chan-rows: always)
+    bool wide;               // fp32 column / chan: 64 x 16 tiles (ofl_warp_wide.hip) instead of 32 x 16 (the 16-bit unit has 64 x 16 only)
+};
+enum WarpKind {
+    kWarpPlain,              // ofl_warp_bwd_f32: a plain warp, an addend (the flow itself: mode 3), src - src_b, the output's flag word -- read off the params
+    kWarpU8,                 // ofl_warp_bwd_u8, a group of up to 3 planes
+    kWarpHalfSrc,            // ofl_warp_bwd_h_f32
+    kWarpGrad,               // the gradient with respect to the flow, fp32 and 16-bit (p.addend is the upstream gradient)
+    kWarpX16,                // ofl_warp_bwd_x16
+};
+
+// A column block lives kLdsT tiles long, and with fewer than ~4.5 blocks per resident slot (256 CUs x 6) the chip idles behind the last
+// ones: large launches (this many four-tile groups) take columns of kLdsT tiles, below that the pair kernel's twice-as-many, half-as-long
+// blocks win: B = 1 / 2 / 4 / 6 at 1080p -4 / -15 / -7 / -5 %, B >= 8 the column kernel by 1-4 % (profiles/r4_small_batch_kernel_choice.txt)
+// ... and a TINY launch (fewer single tiles than that: a 1080p frame at B = 1 has 4 080) takes ONE tile per block: 2.7 short
+// rounds of blocks instead of 1.3 long ones -- B = 1 1080p apply 21.7 -> 19.2 us, mode 3 20.6 -> 18.4 us; from B = 2 the
+// pair kernel is level or ahead (profiles/r4_small_batch_kernel_choice.txt)
+constexpr unsigned kColumnMinGroups = 6912;
+static_assert(kLdsT == 4, "warp_choose counts column groups of four 32 x 16 tiles");
+
+// The kernel of ONE launch: `p` as it will be launched (for more than 3 channels first the whole call -- the channel loop or kWarpSplit --,
+// then each group of 3), the entry point, the path option.  The only reader of OFL_ROWS_T1_MAX, OFL_ROWS_T4_MIN, kColumnMinGroups and
+// OFL_WARP_CHAN_WIDE_MIN; the launchers switch over its answer and decide nothing.
+inline WarpChoice warp_choose(const WarpParams& p, WarpKind kind, int path) {
+    if (!warp_staged(p, path)) return {kWarpGeneric, 1, false, false};
+    const unsigned g1 = warp_tiles(p.n, p.h, p.w, 32, 16), g4 = warp_tiles(p.n, p.h, p.w, 32, 4 * 16);
+    const bool lean = warp_is_lean(p), valid = p.valid != nullptr, automatic = path == kPathAuto;
+    const WarpChoice rows_big = {kWarpRows, OFL_ROWS_T, true, true};
+    // below the four-tile threshold: one tile per block for tiny launches, else two (see OFL_ROWS_T1_MAX)
+    const WarpChoice rows_small = {kWarpRows, (uint8_t)(g1 < OFL_ROWS_T1_MAX ? 1 : 2), true, true};
+    const WarpChoice pair = {kWarpPair, 2, false, false};
+    if (kind == kWarpGrad) {
+        // row tables where the launch is lean: small launches (the shapes training runs at) with one tile per block for tiny ones, else two
+        if (lean && path_rows(path)) {
+            if (g4 >= (automatic ? OFL_ROWS_T4_MIN : kColumnMinGroups) || path == kPathRowColumns) return rows_big;
+            if (automatic) return rows_small;
+        }
+        return {kWarpColumn, kLdsT, false, false};
+    }
+    const bool add = p.addend != nullptr;
+    if (p.c > 3) {
+        // more than 3 channels of a plain warp: ONE launch that walks the channels inside the block (warp_bwd_lds_chan_kernel)
+        // (with the valid area wanted the first group is 3 channels + the mask plane: below 7 channels two launches of 3 are as good or better)
+        const bool loop = (kind == kWarpPlain || (kind == kWarpX16 && lean)) && p.c >= (valid ? 7 : 4) && (p.w & 3) == 0 && !add && !p.src_b && !p.dst_flags &&
+                          path != kPathChannelGroups;
+        if (!loop) return {kWarpSplit, 0, false, false};
+        // 64 x 16 tiles for large launches -- and, with per-row extents (lean, two channel groups or more), for EVERY size: B = 1 C = 64
+        // 0.355 -> 0.255 ms, C = 16 0.071 -> 0.054 ms against the 32 x 16 rectangle version (tools/bench_chan.py --batch 1)
+        // (row extents from two channel groups on: with one group their set-up is not amortised -- C = 4: 0.148 against 0.138 ms)
+        if (path != kPathRectangle && p.c >= 7 && lean) return {kWarpChanRows, 1, true, true};
+        return {kWarpChan, 1, lean, g1 >= OFL_WARP_CHAN_WIDE_MIN};
+    }
+    if (kind == kWarpU8) {              // large launches of 1 or 3 planes with W % 4 == 0: row tables
+        if ((p.c == 1 || p.c == 3) && (p.w & 3) == 0 && path_rows(path) && g4 >= kColumnMinGroups) return rows_big;
+        return pair;
+    }
+    if (kind == kWarpHalfSrc || p.src_b) {      // (src_b: 2 channels, valid mask, no addend, no output flags)
+        // large launches: columns of four tiles -- row tables when lean, else the sheared rectangle's (lean when the promises hold)
+        if (path_columns(path) && g4 >= kColumnMinGroups) return (lean && path != kPathRectangle) ? rows_big : WarpChoice{kWarpColumn, kLdsT, lean, false};
+        return pair;
+    }
+    if (p.dst_flags) {                  // (2 channels, only with a valid mask) large lean launches: the row-table kernel keeps the flag by-product
+        if (valid && path_rows(path) && lean && g4 >= kColumnMinGroups) return rows_big;
+        return pair;
+    }
+    // the fused composition (an addend): row tables where the launch is lean, else -- large launches only -- the four-tile column kernels
+    // (REUSE / lean twins: no scratch since round 5); small and forced-path launches fall through to the pair / one-tile kernels
+    if (add && p.c == 2 && !p.flow_flags) {
+        // large launches of mode 3 proper and of another addend: 64 x 16 tiles with per-row extents (warp_bwd_rows_kernel<.., ADD>)
+        if (lean && path_rows(path) && g4 >= (automatic && p.add_is_flow ? OFL_ROWS_T4_MIN : kColumnMinGroups)) return rows_big;
+        if (p.add_is_flow && lean && g4 < OFL_ROWS_T4_MIN && automatic) return rows_small;     // small mode 3
+        // the four-tile column kernels are for LARGE launches on the automatic path (small launches keep the pair /
+        // one-tile kernels further down -- half as many, twice as long blocks lose there -- and OFL_OPT_WARP_PATH 3 / 4 must reach them)
+        if (g4 >= kColumnMinGroups && path_columns(path)) return {kWarpColumn, kLdsT, lean, false};
+    }
+    // a plain warp (Flow.apply 't' of an image or a flow)
+    if (path == kPathRowColumns && !add && lean) return rows_big;   // (tests / experiments: four-tile columns with row tables whatever the size)
+    // small plain launches on the row-table kernel (1 tile per block for tiny ones, else 2): B = 2 ... 6 at 1080p -13 ... -14 % against the
+    // two-tile kernel on the sheared rectangle (53 -> 62 %, 58 -> 68 %, 61 -> 71 % of 8 TB/s; tools/small_once.py), B = 1 -1.5 %
+    if (!add && automatic && lean) {
+        if (g4 < OFL_ROWS_T4_MIN) return rows_small;
+        if (g4 < kColumnMinGroups) return rows_big;      // (four tiles per block a little earlier than the rectangle's kernels: B = 6 at 1080p 76.5 -> 74.5 us)
+    }
+    if (path == kPathOneTile || (path != kPathPair && g1 < kColumnMinGroups))
+        return {kWarpColumn, 1, lean && valid, false};  // (lean twins of the instantiations with a valid mask only: BASELINE configs[1] is one of them)
+    if (!add && !p.flow_flags && g4 >= kColumnMinGroups && path != kPathPair)
+        return (lean && path != kPathRectangle) ? rows_big : WarpChoice{kWarpColumn, kLdsT, lean, true};    // 64 x 16 tiles: -1.9 % (see kLdsNT)
+    return pair;
+}
+
+// run-time flags and counts as template arguments: the statement is written once and compiled for every value.  ONLY where every
+// combination is a kernel the library has anyway -- elsewhere the cases are written out, so that no instantiation is added
+#define OFL_WITH_BOOL(flag_, B_, ...) do { if (flag_) { constexpr bool B_ = true; __VA_ARGS__; } else { constexpr bool B_ = false; __VA_ARGS__; } } while (0)
+#define OFL_WITH_NC(nc_, N_, ...) do { switch (nc_) { case 1: { constexpr int N_ = 1; __VA_ARGS__; } break; case 2: { constexpr int N_ = 2; __VA_ARGS__; } break; \
+                                                    default: { constexpr int N_ = 3; __VA_ARGS__; } break; } } while (0)
+// (tiles per block of the row-table kernel: 1, 2 or OFL_ROWS_T)
+#define OFL_WITH_ROWS_T(tiles_, T_, ...) do { if ((tiles_) == OFL_ROWS_T) { constexpr int T_ = OFL_ROWS_T; __VA_ARGS__; } else if ((tiles_) == 1) { constexpr int T_ = 1; __VA_ARGS__; } \
+                                              else { constexpr int T_ = 2; __VA_ARGS__; } } while (0)
+
 #if defined(OFL_SPLAT_TU)
 }  // namespace
 
@@ -3863,74 +4019,40 @@ extern "C" __attribute__((visibility("default"))) int ofl_debug_rows_stamps(unsi
     return 0;
 }
 #endif
-int ofl_wide_launch_column(const void* params, int nc, int valid, int add, int rows, void* stream) {
+int ofl_wide_launch_column(const void* params, int nc, void* stream) {
     WarpParams q = *static_cast<const WarpParams*>(params);
     q.lds_bytes = kLdsBytes;
+    if (q.addend || q.src_b || q.dst_flags) return (int)hipErrorInvalidValue;     // (a plain warp only: the other column kernels run on 32 x 16 tiles)
     const unsigned g = warp_geometry(q, kLdsTWQ * 4, kLdsT * kLdsTH);
     hipStream_t st = (hipStream_t)stream;
-    constexpr int TT = kLdsT > 2 ? kLdsT : 3;
-    const bool lean = warp_is_lean(q);
-    constexpr int RT = OFL_ROWS_T;                                // tiles per column of the row-table kernel
-    if (rows && lean && nc == 2 && (add || q.src_b || q.dst_flags)) {      // the flow-level variants with per-row extents
-        const unsigned gr = RT == TT ? g : warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH);
-        const int am = !add ? 0 : (q.add_is_flow ? 1 : 2);
-#define OFL_ROWS_F(V, A, S, D) OFL_KLAUNCH((warp_bwd_rows_kernel<RT, 2, V, A, S, D>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, st, q)
-        if (q.src_b) { if (!valid || add || q.dst_flags) return (int)hipErrorInvalidValue; OFL_ROWS_F(true, 0, true, false); }          // mode 1 't': src - src_b
-        else if (q.dst_flags) {                                    // (host: only with a valid mask)
-            if (!valid) return (int)hipErrorInvalidValue;
-            if (am == 0) OFL_ROWS_F(true, 0, false, true); else if (am == 1) OFL_ROWS_F(true, 1, false, true); else OFL_ROWS_F(true, 2, false, true);
-        } else if (am == 1) { if (valid) OFL_ROWS_F(true, 1, false, false); else OFL_ROWS_F(false, 1, false, false); }                  // mode 3 proper
-        else { if (valid) OFL_ROWS_F(true, 2, false, false); else OFL_ROWS_F(false, 2, false, false); }                                 // another addend
-#undef OFL_ROWS_F
-        return (int)hipGetLastError();
-    }
-    if (rows && lean && !add) {                  // per-row extents instead of one sheared rectangle (warp_bwd_rows_kernel)
-        const unsigned gr = RT == TT ? g : warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH);
-#define OFL_ROWS_CASE(NC)                                                                                                    \
-        if (valid) OFL_KLAUNCH((warp_bwd_rows_kernel<RT, NC, true>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, st, q);   \
-        else OFL_KLAUNCH((warp_bwd_rows_kernel<RT, NC, false>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, st, q);
-        switch (nc) {
-            case 1: OFL_ROWS_CASE(1) break;
-            case 2: OFL_ROWS_CASE(2) break;
-            default: OFL_ROWS_CASE(3) break;
-        }
-#undef OFL_ROWS_CASE
-        return (int)hipGetLastError();
-    }
-    if (add) return (int)hipErrorInvalidValue;     // (callers route an addend here only when the row-table kernel above takes it)
-#define OFL_WIDE_CASE(NC)                                                                                                                   \
-    if (lean) {                                                                                                                              \
-        if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, NC, true, false, false, false, float, float, false, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);   \
-        else OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, NC, false, false, false, false, float, float, false, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);        \
-    } else if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, NC, true, false>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);      \
-    else OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, NC, false, false>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-    switch (nc) {
-        case 1: OFL_WIDE_CASE(1) break;
-        case 2: OFL_WIDE_CASE(2) break;
-        default: OFL_WIDE_CASE(3) break;
-    }
-#undef OFL_WIDE_CASE
+    const bool valid = q.valid != nullptr, lean = warp_is_lean(q);
+    OFL_WITH_NC(nc, NC, OFL_WITH_BOOL(valid, V, OFL_WITH_BOOL(lean, LN,
+        OFL_KLAUNCH((warp_bwd_lds_column_kernel<kLdsT, NC, V, false, false, false, float, float, false, false, LN>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q))));
     return (int)hipGetLastError();
 }
 
-// SMALL plain lean launches (below the four-tile column's threshold): the row-table kernel with one tile (tiny: B = 1 at 1080p) or two
-// tiles per block -- B = 2 ... 6 at 1080p: -13 ... -14 % against the two-tile kernel on the sheared rectangle (53 -> 62 %, 58 -> 68 %,
-// 61 -> 71 % of 8 TB/s; tools/small_once.py), B = 1 -1.5 %.  1 ... 3 channels and mode 3 proper.
-int ofl_wide_launch_rows_small(const void* params, int nc, int valid, int add, int tiles, void* stream) {
+// The row-table kernel on fp32 planes: per-row extents instead of one sheared rectangle (warp_bwd_rows_kernel; lean launches only).  Plain
+// warps of 1 ... 3 channels and mode 3 proper at every tile count -- SMALL launches (below the four-tile threshold) with one tile (tiny:
+// B = 1 at 1080p) or two tiles per block --, the other flow-level variants (another addend, src - src_b, the output's flag word) at
+// OFL_ROWS_T tiles only.
+int ofl_wide_launch_rows(const void* params, int nc, int tiles, void* stream) {
     WarpParams q = *static_cast<const WarpParams*>(params);
     q.lds_bytes = kLdsBytes;
     hipStream_t st = (hipStream_t)stream;
-    if (!warp_is_lean(q) || q.src_b || q.dst_flags || nc < 1 || nc > 3 || (add && !(nc == 2 && q.add_is_flow))) return (int)hipErrorInvalidValue;
-    const unsigned gs = warp_geometry(q, kLdsTWQ * 4, (tiles == 1 ? 1 : 2) * kLdsTH);
-#define OFL_ROWS_S(T_, NC, V, A) OFL_KLAUNCH((warp_bwd_rows_kernel<T_, NC, V, A>), dim3(gs), dim3(kLdsNT), kRowsLdsBytes, st, q)
-#define OFL_ROWS_ST(T_)                                                                                   \
-    if (add) { if (valid) OFL_ROWS_S(T_, 2, true, 1); else OFL_ROWS_S(T_, 2, false, 1); }                \
-    else if (nc == 2) { if (valid) OFL_ROWS_S(T_, 2, true, 0); else OFL_ROWS_S(T_, 2, false, 0); }       \
-    else if (nc == 1) { if (valid) OFL_ROWS_S(T_, 1, true, 0); else OFL_ROWS_S(T_, 1, false, 0); }       \
-    else { if (valid) OFL_ROWS_S(T_, 3, true, 0); else OFL_ROWS_S(T_, 3, false, 0); }
-    if (tiles == 1) { OFL_ROWS_ST(1) } else { OFL_ROWS_ST(2) }
-#undef OFL_ROWS_ST
-#undef OFL_ROWS_S
+    constexpr int RT = OFL_ROWS_T;                                // tiles per column of large launches
+    const bool valid = q.valid != nullptr, big = tiles == RT;
+    const int am = !q.addend ? 0 : (q.add_is_flow ? 1 : 2);
+    const bool flow_level = am == 2 || q.src_b || q.dst_flags;      // the variants that exist at OFL_ROWS_T tiles only
+    if (!warp_is_lean(q) || nc < 1 || nc > 3 || ((am || flow_level) && nc != 2) || (flow_level && !big)) return (int)hipErrorInvalidValue;
+    if (q.src_b ? (!valid || am || q.dst_flags) : (q.dst_flags && !valid)) return (int)hipErrorInvalidValue;      // (host: both only with a valid mask)
+    const unsigned gr = warp_geometry(q, kLdsTWQ * 4, (big ? RT : tiles == 1 ? 1 : 2) * kLdsTH);
+#define OFL_ROWS(T_, NC, V, A, S, D) OFL_KLAUNCH((warp_bwd_rows_kernel<T_, NC, V, A, S, D>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, st, q)
+    if (q.src_b) OFL_ROWS(RT, 2, true, 0, true, false);                                                           // mode 1 't': src - src_b
+    else if (q.dst_flags) { if (am == 0) OFL_ROWS(RT, 2, true, 0, false, true); else if (am == 1) OFL_ROWS(RT, 2, true, 1, false, true); else OFL_ROWS(RT, 2, true, 2, false, true); }
+    else if (am == 2) OFL_WITH_BOOL(valid, V, OFL_ROWS(RT, 2, V, 2, false, false));                               // another addend
+    else if (am == 1) OFL_WITH_ROWS_T(tiles, T, OFL_WITH_BOOL(valid, V, OFL_ROWS(T, 2, V, 1, false, false)));     // mode 3 proper
+    else OFL_WITH_ROWS_T(tiles, T, OFL_WITH_NC(nc, NC, OFL_WITH_BOOL(valid, V, OFL_ROWS(T, NC, V, 0, false, false))));
+#undef OFL_ROWS
     return (int)hipGetLastError();
 }
 // a flow stored in fp16 gathered from its halves (ofl_warp_bwd_h_f32), large lean launches: the row-table kernel
@@ -3938,25 +4060,19 @@ int ofl_wide_launch_rows_h(const void* params, void* stream) {
     WarpParams q = *static_cast<const WarpParams*>(params);
     q.lds_bytes = kLdsBytes;
     constexpr int RT = OFL_ROWS_T;
-    const unsigned gr = warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH);
     if (!warp_is_lean(q) || !q.valid || q.addend || q.dst_flags) return OFL_E_UNSUPPORTED;     // (not this kernel's launch: the caller takes the column / pair kernel)
-    if (q.src_b) OFL_KLAUNCH((warp_bwd_rows_kernel<RT, 2, true, 0, true, false, _Float16>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q);
-    else OFL_KLAUNCH((warp_bwd_rows_kernel<RT, 2, true, 0, false, false, _Float16>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q);
+    const unsigned gr = warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH);
+    OFL_WITH_BOOL(q.src_b != nullptr, SB, OFL_KLAUNCH((warp_bwd_rows_kernel<RT, 2, true, 0, SB, false, _Float16>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q));
     return (int)hipGetLastError();
 }
-// the gradient with respect to the flow (ofl_warp_bwd_grad_f32), large launches with W % 4 == 0: the row-table kernel
+// the gradient with respect to the flow (ofl_warp_bwd_grad_f32), launches with W % 4 == 0: the row-table kernel
 int ofl_wide_launch_rows_grad(const void* params, int nc, int tiles, void* stream) {      // tiles per block: OFL_ROWS_T for large launches, 1 / 2 for tiny / small ones
     WarpParams q = *static_cast<const WarpParams*>(params);
     q.lds_bytes = kLdsBytes;
-    constexpr int RT = OFL_ROWS_T;
-    const int tt = tiles == 1 ? 1 : (tiles == 2 ? 2 : RT);
-    const unsigned gr = warp_geometry(q, kLdsTWQ * 4, tt * kLdsTH);
     if (!warp_is_lean(q) || q.valid || q.src_b || q.dst_flags) return OFL_E_UNSUPPORTED;
-#define OFL_ROWS_G(T_, NC) OFL_KLAUNCH((warp_bwd_rows_kernel<T_, NC, false, 0, false, false, float, float, false, true>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q)
-#define OFL_ROWS_GT(T_) switch (nc) { case 1: OFL_ROWS_G(T_, 1); break; case 2: OFL_ROWS_G(T_, 2); break; default: OFL_ROWS_G(T_, 3); break; }
-    if (tt == 1) { OFL_ROWS_GT(1) } else if (tt == 2) { OFL_ROWS_GT(2) } else { OFL_ROWS_GT(RT) }
-#undef OFL_ROWS_GT
-#undef OFL_ROWS_G
+    const unsigned gr = warp_geometry(q, kLdsTWQ * 4, (tiles == OFL_ROWS_T ? OFL_ROWS_T : tiles == 1 ? 1 : 2) * kLdsTH);
+    OFL_WITH_ROWS_T(tiles, T, OFL_WITH_NC(nc, NC,
+        OFL_KLAUNCH((warp_bwd_rows_kernel<T, NC, false, 0, false, false, float, float, false, true>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q)));
     return (int)hipGetLastError();
 }
 // uint8 images warped from and to their bytes (ofl_warp_bwd_u8; 1 or 3 channels, W % 4 == 0), large launches: the row-table kernel
@@ -3964,78 +4080,63 @@ int ofl_wide_launch_rows_u8(const void* params, int nc, int dst_is_u8, void* str
     WarpParams q = *static_cast<const WarpParams*>(params);
     q.lds_bytes = kLdsBytes;
     constexpr int RT = OFL_ROWS_T;
-    const unsigned gr = warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH);
     if ((q.w & 3) != 0 || q.flow_flags || q.addend || q.src_b || q.dst_flags || !(nc == 1 || nc == 3)) return OFL_E_UNSUPPORTED;
-#define OFL_ROWS_U8(NC, V, TD) OFL_KLAUNCH((warp_bwd_rows_kernel<RT, NC, V, 0, false, false, uint8_t, TD, true>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q)
-    if (dst_is_u8) {
-        if (nc == 1) { if (q.valid) OFL_ROWS_U8(1, true, uint8_t); else OFL_ROWS_U8(1, false, uint8_t); }
-        else { if (q.valid) OFL_ROWS_U8(3, true, uint8_t); else OFL_ROWS_U8(3, false, uint8_t); }
-    } else {                                          // (Flow.apply of a uint8 image: fp32 out, rounded or not as the caller says)
-        if (nc == 1) { if (q.valid) OFL_ROWS_U8(1, true, float); else OFL_ROWS_U8(1, false, float); }
-        else { if (q.valid) OFL_ROWS_U8(3, true, float); else OFL_ROWS_U8(3, false, float); }
-    }
+    const unsigned gr = warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH);
+#define OFL_ROWS_U8(NC, TD) OFL_WITH_BOOL(q.valid != nullptr, V, OFL_KLAUNCH((warp_bwd_rows_kernel<RT, NC, V, 0, false, false, uint8_t, TD, true>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q))
+    if (dst_is_u8) { if (nc == 1) OFL_ROWS_U8(1, uint8_t); else OFL_ROWS_U8(3, uint8_t); }
+    else { if (nc == 1) OFL_ROWS_U8(1, float); else OFL_ROWS_U8(3, float); }            // (Flow.apply of a uint8 image: fp32 out, rounded or not as the caller says)
 #undef OFL_ROWS_U8
     return (int)hipGetLastError();
 }
-int ofl_wide_launch_chan(const void* params, int valid, int rows, void* stream) {
+int ofl_wide_launch_chan(const void* params, int rows, void* stream) {
     WarpParams q = *static_cast<const WarpParams*>(params);
     q.lds_bytes = kLdsBytes;
+    const bool valid = q.valid != nullptr, lean = warp_is_lean(q);
     const unsigned g1 = warp_geometry(q, kLdsTWQ * 4, kLdsTH);
-    if (rows && warp_is_lean(q)) {
-        if (valid) OFL_KLAUNCH((warp_bwd_lds_chan_kernel<true, true, 1, true>), dim3(g1), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q);
-        else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, true, 1, true>), dim3(g1), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q);
-        return (int)hipGetLastError();
-    }
-    if (warp_is_lean(q)) {
-        if (valid) OFL_KLAUNCH((warp_bwd_lds_chan_kernel<true, true>), dim3(g1), dim3(kLdsNT), kLdsBytes, (hipStream_t)stream, q);
-        else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, true>), dim3(g1), dim3(kLdsNT), kLdsBytes, (hipStream_t)stream, q);
-    } else if (valid) OFL_KLAUNCH((warp_bwd_lds_chan_kernel<true>), dim3(g1), dim3(kLdsNT), kLdsBytes, (hipStream_t)stream, q);
-    else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false>), dim3(g1), dim3(kLdsNT), kLdsBytes, (hipStream_t)stream, q);
+    if (rows && lean) OFL_WITH_BOOL(valid, V, OFL_KLAUNCH((warp_bwd_lds_chan_kernel<V, true, 1, true>), dim3(g1), dim3(kLdsNT), kRowsLdsBytes, (hipStream_t)stream, q));
+    else OFL_WITH_BOOL(valid, V, OFL_WITH_BOOL(lean, LN, OFL_KLAUNCH((warp_bwd_lds_chan_kernel<V, LN>), dim3(g1), dim3(kLdsNT), kLdsBytes, (hipStream_t)stream, q)));
     return (int)hipGetLastError();
 }
 #elif defined(OFL_X16_TU)
 // This translation unit (ofl_warp_half.hip) provides ofl_warp_bwd_x16: the plain backward warp of planes STORED in fp16 / bf16 (feature
 // tensors under autocast), on the TS = TD = half_t / bf16_t instantiations of the staged kernels above, 64 x 16 tiles.  The launch
-// decisions follow launch_warp_lds / warp_bwd_impl (thresholds in THEIR 32-wide geometry, so that a 16-bit call changes kernel where
-// the fp32 call does), with fewer branches: lean launches (W % 4 == 0) of up to 3 planes run the row-table kernel with 1 / 2 / 4 tiles
-// per block, the others the sheared rectangle's one-tile / pair / four-tile kernels; from 4 planes on (7 with the valid area) the
-// channel loop.  What a kernel here cannot take is declined (OFL_E_UNSUPPORTED) and the caller converts and calls ofl_warp_bwd_f32.
-constexpr unsigned kX16ColumnMin = 6912;       // (kColumnMinGroups of launch_warp_lds)
-inline unsigned x16_tiles(const WarpParams& p, int tw, int th) {   // blocks of a launch on tw x th tiles (warp_geometry's count)
-    const int64_t t = (int64_t)((p.w + tw - 1) / tw) * ((p.h + th - 1) / th) * p.n;
-    return (unsigned)(((t + kXcds - 1) / kXcds) * kXcds);
-}
+// decisions are warp_choose()'s, the fp32 entry point's own (thresholds in the 32-wide geometry, so that a 16-bit call changes kernel
+// where the fp32 call does): lean launches (W % 4 == 0) of up to 3 planes run the row-table kernel with 1 / 2 / 4 tiles per block, the
+// others the sheared rectangle's one-tile / pair / four-tile kernels (no lean twins, 64 x 16 tiles whatever `wide` says); from 4 planes
+// on (7 with the valid area) the channel loop.  What a kernel here cannot take is declined (OFL_E_UNSUPPORTED) and the caller converts
+// and calls ofl_warp_bwd_f32.
 template <typename TX, int NC, bool V>
-int x16_launch_group(const WarpParams& p, hipStream_t st) {
+int x16_launch_group(const WarpParams& p, WarpChoice ch, hipStream_t st) {
     WarpParams q = p;
-    const unsigned g1 = x16_tiles(p, 32, 16), g4 = x16_tiles(p, 32, 64);
-    constexpr int TT = kLdsT > 2 ? kLdsT : 3, RT = OFL_ROWS_T;
-    if (warp_is_lean(q)) {
-        if (g4 >= OFL_ROWS_T4_MIN) OFL_KLAUNCH((warp_bwd_rows_kernel<RT, NC, V, 0, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, RT * kLdsTH)), dim3(kLdsNT), kRowsLdsBytes, st, q);
-        else if (g1 < OFL_ROWS_T1_MAX) OFL_KLAUNCH((warp_bwd_rows_kernel<1, NC, V, 0, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, kLdsTH)), dim3(kLdsNT), kRowsLdsBytes, st, q);
-        else OFL_KLAUNCH((warp_bwd_rows_kernel<2, NC, V, 0, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, 2 * kLdsTH)), dim3(kLdsNT), kRowsLdsBytes, st, q);
-        return (int)hipGetLastError();
+    const unsigned g = warp_geometry(q, kLdsTWQ * 4, ch.tiles * kLdsTH);
+    switch (ch.family) {
+        case kWarpRows:
+            OFL_WITH_ROWS_T(ch.tiles, T, OFL_KLAUNCH((warp_bwd_rows_kernel<T, NC, V, 0, false, false, TX, TX>), dim3(g), dim3(kLdsNT), kRowsLdsBytes, st, q));
+            break;
+        // a width that is no multiple of 4 (or no shear: a frame too wide for 16-bit sheared rows): the sheared rectangle / plain box
+        case kWarpColumn:
+            if (ch.tiles == 1) OFL_KLAUNCH((warp_bwd_lds_column_kernel<1, NC, V, false, false, false, TX, TX>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+            else OFL_KLAUNCH((warp_bwd_lds_column_kernel<kLdsT, NC, V, false, false, false, TX, TX>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+            break;
+        case kWarpPair:
+            OFL_KLAUNCH((warp_bwd_lds_kernel<NC, V, false, false, false, TX, TX>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+            break;
+        default: return OFL_E_UNSUPPORTED;
     }
-    // a width that is no multiple of 4 (or no shear: a frame too wide for 16-bit sheared rows): the sheared rectangle / plain box
-    if (g1 < kX16ColumnMin) OFL_KLAUNCH((warp_bwd_lds_column_kernel<1, NC, V, false, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, kLdsTH)), dim3(kLdsNT), kLdsBytes, st, q);
-    else if (g4 >= kX16ColumnMin) OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, NC, V, false, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, TT * kLdsTH)), dim3(kLdsNT), kLdsBytes, st, q);
-    else OFL_KLAUNCH((warp_bwd_lds_kernel<NC, V, false, false, false, TX, TX>), dim3(warp_geometry(q, kLdsTWQ * 4, 2 * kLdsTH)), dim3(kLdsNT), kLdsBytes, st, q);
     return (int)hipGetLastError();
 }
 template <typename TX>
-int x16_launch(WarpParams p, const void* src, void* dst, hipStream_t st) {
+int x16_launch(WarpParams p, const void* src, void* dst, int path, hipStream_t st) {
     const int32_t c = p.c;
     const int64_t hw = (int64_t)p.h * p.w;
     p.src = reinterpret_cast<const float*>(src); p.dst = reinterpret_cast<float*>(dst);      // (the kernels re-read these as TX pointers)
-    // more than 3 planes: ONE launch that walks them inside the block (see warp_bwd_impl: 7 with the valid area; per-row extents from
-    // two channel groups on)
-    if (c >= (p.valid ? 7 : 4) && warp_is_lean(p)) {
+    // more than 3 planes: ONE launch that walks them inside the block where warp_choose() says so
+    const WarpChoice whole = c > 3 ? warp_choose(p, kWarpX16, path) : WarpChoice{kWarpSplit, 0, false, false};
+    if (whole.family == kWarpChanRows || whole.family == kWarpChan) {
         WarpParams q = p;
         const unsigned g1 = warp_geometry(q, kLdsTWQ * 4, kLdsTH);
-        if (c >= 7) {
-            if (q.valid) OFL_KLAUNCH((warp_bwd_lds_chan_kernel<true, true, 1, true, TX, TX>), dim3(g1), dim3(kLdsNT), kRowsLdsBytes, st, q);
-            else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, true, 1, true, TX, TX>), dim3(g1), dim3(kLdsNT), kRowsLdsBytes, st, q);
-        } else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, true, 1, false, TX, TX>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q);
+        if (whole.family == kWarpChanRows) OFL_WITH_BOOL(q.valid != nullptr, V, OFL_KLAUNCH((warp_bwd_lds_chan_kernel<V, true, 1, true, TX, TX>), dim3(g1), dim3(kLdsNT), kRowsLdsBytes, st, q));
+        else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, true, 1, false, TX, TX>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q);     // (4 ... 6 planes: the loop only without the valid area)
         return (int)hipGetLastError();
     }
     // otherwise groups of 3; the valid mask comes out of the first group
@@ -4046,9 +4147,9 @@ int x16_launch(WarpParams p, const void* src, void* dst, hipStream_t st) {
         q.src = reinterpret_cast<const float*>(static_cast<const TX*>(src) + c0 * hw);
         q.dst = reinterpret_cast<float*>(static_cast<TX*>(dst) + c0 * hw);
         if (c0 > 0) { q.valid = nullptr; q.src_mask = nullptr; }
+        const WarpChoice ch = warp_choose(q, kWarpX16, path);
         int rc;
-        if (q.valid) rc = nc == 1 ? x16_launch_group<TX, 1, true>(q, st) : nc == 2 ? x16_launch_group<TX, 2, true>(q, st) : x16_launch_group<TX, 3, true>(q, st);
-        else rc = nc == 1 ? x16_launch_group<TX, 1, false>(q, st) : nc == 2 ? x16_launch_group<TX, 2, false>(q, st) : x16_launch_group<TX, 3, false>(q, st);
+        OFL_WITH_NC(nc, NC, OFL_WITH_BOOL(q.valid != nullptr, V, rc = x16_launch_group<TX, NC, V>(q, ch, st)));
         if (rc) return rc;
     }
     return OFL_OK;
@@ -4068,29 +4169,24 @@ extern "C" __attribute__((visibility("default"))) int ofl_warp_bwd_x16(
     if (dtype != OFL_X16_HALF && dtype != OFL_X16_BFLOAT) return OFL_E_ARG;
     if (round_mode < 0 || round_mode > 2) return OFL_E_ARG;
     if (!(flow_sign == 1.0f || flow_sign == -1.0f)) return OFL_E_ARG;
-    if ((int64_t)((w + 31) / 32) * ((h + 15) / 16) * n >= (1ll << 31)) return OFL_E_SHAPE;
+    if (warp_tiles_overflow(n, h, w)) return OFL_E_SHAPE;
     // the plain warp only: no addend, no subtracted source, no flag words, no rounding (and no flow window: ofl_warp_bwd_win_f32)
     if (src_b || addend || flow_flags || src_flags || dst_flags || round_mode != OFL_ROUND_NONE) return OFL_E_UNSUPPORTED;
-    // staged kernels only (the conditions of warp_bwd_impl), on the automatic path (OFL_OPT_WARP_PATH picks among the fp32 kernels)
-    if (!(ofl_warp_path_option() == 0 && w >= 4 && h >= 2 && w < 32760 && h < 32760 && (int64_t)h * w < (1ll << 24))) return OFL_E_UNSUPPORTED;
-    WarpParams p = {};
-    p.flow = flow; p.flow_bs = flow_bs; p.src_bs = src_bs;
+    // staged kernels only, on the automatic path (OFL_OPT_WARP_PATH picks among the fp32 kernels)
+    const int path = ofl_warp_path_option();
+    if (!(path == kPathAuto && warp_frame_staged(h, w))) return OFL_E_UNSUPPORTED;
+    WarpParams p;
+    warp_params_init(p, n, c, h, w, flow, flow_bs, flow_sign);
+    p.src_bs = src_bs;
     p.src_mask = src_mask; p.src_mask_bs = src_mask_bs; p.flow_mask = flow_mask; p.flow_mask_bs = flow_mask_bs;
     p.valid = valid;
-    p.n = n; p.c = c; p.h = h; p.w = w;
-    p.flow_sign = flow_sign; p.a_sign = 1.0f; p.g_sign = 1.0f; p.round_mode = OFL_ROUND_NONE;
-    p.wm1 = (float)(w - 1); p.hm1 = (float)(h - 1);
-    p.half_wm1 = p.wm1 / 2.0f; p.half_hm1 = p.hm1 / 2.0f;
-    p.rcp_wm1 = 1.0f / p.wm1; p.rcp_hm1 = 1.0f / p.hm1;
-    p.lds_bytes = kLdsBytes;
-    p.shear = (ofl_warp_shear_option() && (int64_t)h + 4 * (int64_t)w + 8 < 32760) ? 1 : 0;
     p.dst_bs = (int64_t)c * h * w;
-    return dtype == OFL_X16_HALF ? x16_launch<half_t>(p, src, dst, (hipStream_t)stream) : x16_launch<bf16_t>(p, src, dst, (hipStream_t)stream);
+    return dtype == OFL_X16_HALF ? x16_launch<half_t>(p, src, dst, path, (hipStream_t)stream) : x16_launch<bf16_t>(p, src, dst, path, (hipStream_t)stream);
 }
 
 // ---- ofl_warp_bwd_grad_x16: the gradient of that warp with respect to its FLOW, from the 16-bit source and the 16-bit upstream gradient ----
 // Up to 3 planes: the GRAD instantiations of the staged kernels on TS = half_t / bf16_t (taps and upstream gradient up-converted at the
-// load, the fp32 sums of lds_gather_impl, fp32 grad_flow), picked as ofl_internal_warp_grad_flow_lds picks the fp32 ones -- row tables
+// load, the fp32 sums of lds_gather_impl, fp32 grad_flow), picked by warp_choose() as for ofl_internal_warp_grad_flow_lds -- row tables
 // with 1 / 2 / 4 tiles per block where the launch is lean, else the four-tile column kernel on the sheared rectangle.  More planes: the
 // sums run over ALL planes in one chain per pixel (the order of warp_grad_kernel, ofl_aux_kernels.hip, which the fp32 entry point takes
 // there), so they cannot be split into launches of 3: one pixel per lane, the same expressions, 2-byte gathers.
@@ -4132,25 +4228,17 @@ __global__ __launch_bounds__(256) void warp_grad_flow_x16_kernel(const float* __
 }
 
 template <typename TX, int NC>
-int x16_grad_staged(const WarpParams& p, hipStream_t st) {
+int x16_grad_staged(const WarpParams& p, int path, hipStream_t st) {
     WarpParams q = p;
-    const unsigned g1 = x16_tiles(p, 32, 16), g4 = x16_tiles(p, 32, 64);
-    constexpr int TT = kLdsT > 2 ? kLdsT : 3, RT = OFL_ROWS_T;
-    if (warp_is_lean(q)) {
-        const int tt = g4 >= OFL_ROWS_T4_MIN ? RT : (g1 < OFL_ROWS_T1_MAX ? 1 : 2);
-        const unsigned gr = warp_geometry(q, kLdsTWQ * 4, tt * kLdsTH);
-#define OFL_X16_RG(T_) OFL_KLAUNCH((warp_bwd_rows_kernel<T_, NC, false, 0, false, false, TX, float, false, true>), dim3(gr), dim3(kLdsNT), kRowsLdsBytes, st, q)
-        if (tt == 1) OFL_X16_RG(1); else if (tt == 2) OFL_X16_RG(2); else OFL_X16_RG(RT);
-#undef OFL_X16_RG
-        return (int)hipGetLastError();
-    }
-    const unsigned g = warp_geometry(q, kLdsTWQ * 4, TT * kLdsTH);
-    OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, NC, false, false, false, false, TX, float, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
+    const WarpChoice ch = warp_choose(p, kWarpGrad, path);
+    const unsigned g = warp_geometry(q, kLdsTWQ * 4, ch.tiles * kLdsTH);
+    if (ch.family == kWarpRows) OFL_WITH_ROWS_T(ch.tiles, T, OFL_KLAUNCH((warp_bwd_rows_kernel<T, NC, false, 0, false, false, TX, float, false, true>), dim3(g), dim3(kLdsNT), kRowsLdsBytes, st, q));
+    else OFL_KLAUNCH((warp_bwd_lds_column_kernel<kLdsT, NC, false, false, false, false, TX, float, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
     return (int)hipGetLastError();
 }
 template <typename TX>
-int x16_grad_launch(const WarpParams& p, float* grad_flow, hipStream_t st) {
-    if (p.c <= 3) return p.c == 1 ? x16_grad_staged<TX, 1>(p, st) : p.c == 2 ? x16_grad_staged<TX, 2>(p, st) : x16_grad_staged<TX, 3>(p, st);
+int x16_grad_launch(const WarpParams& p, float* grad_flow, int path, hipStream_t st) {
+    if (p.c <= 3) return p.c == 1 ? x16_grad_staged<TX, 1>(p, path, st) : p.c == 2 ? x16_grad_staged<TX, 2>(p, path, st) : x16_grad_staged<TX, 3>(p, path, st);
     const int64_t hw = (int64_t)p.h * p.w;
     int64_t bx = (hw + 255) / 256, cap = 8192 / p.n;           // (the grid of warp_grad_kernel: blocks_for, ofl_aux_kernels.hip)
     cap = cap < 64 ? 64 : cap;
@@ -4172,141 +4260,67 @@ extern "C" __attribute__((visibility("default"))) int ofl_warp_bwd_grad_x16(
     if (!(flow_sign == 1.0f || flow_sign == -1.0f)) return OFL_E_ARG;
     if (flow_bs < 0 || src_bs < 0) return OFL_E_ARG;
     if ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(grad_out)) & 1u) return OFL_E_ARG;
-    if ((int64_t)((w + 31) / 32) * ((h + 15) / 16) * n >= (1ll << 31)) return OFL_E_SHAPE;
+    if (warp_tiles_overflow(n, h, w)) return OFL_E_SHAPE;
     // the frames of the staged kernels, on the automatic path (what ofl_warp_bwd_grad_f32 gives its one-pixel-per-lane kernel for the
     // FRAME's sake -- W < 4, H < 2, 2^24 pixels -- is declined: the caller converts and calls it)
-    if (!(ofl_warp_path_option() == 0 && w >= 4 && h >= 2 && w < 32760 && h < 32760 && (int64_t)h * w < (1ll << 24))) return OFL_E_UNSUPPORTED;
-    WarpParams p = {};
-    p.flow = flow; p.flow_bs = flow_bs; p.src = reinterpret_cast<const float*>(src); p.src_bs = src_bs;
+    const int path = ofl_warp_path_option();
+    if (!(path == kPathAuto && warp_frame_staged(h, w))) return OFL_E_UNSUPPORTED;
+    WarpParams p;
+    warp_params_init(p, n, c, h, w, flow, flow_bs, flow_sign);
+    p.src = reinterpret_cast<const float*>(src); p.src_bs = src_bs;
     p.addend = reinterpret_cast<const float*>(grad_out); p.addend_bs = (int64_t)c * h * w;      // (the kernels re-read both as 16-bit planes)
     p.dst = grad_flow; p.dst_bs = (int64_t)2 * h * w;
-    p.n = n; p.c = c; p.h = h; p.w = w;
-    p.flow_sign = flow_sign; p.a_sign = 1.0f; p.g_sign = g_scale; p.round_mode = OFL_ROUND_NONE;
-    p.wm1 = (float)(w - 1); p.hm1 = (float)(h - 1);
-    p.half_wm1 = p.wm1 / 2.0f; p.half_hm1 = p.hm1 / 2.0f;
-    p.rcp_wm1 = 1.0f / p.wm1; p.rcp_hm1 = 1.0f / p.hm1;
-    p.lds_bytes = kLdsBytes;
-    p.shear = (ofl_warp_shear_option() && (int64_t)h + 4 * (int64_t)w + 8 < 32760) ? 1 : 0;
-    return dtype == OFL_X16_HALF ? x16_grad_launch<half_t>(p, grad_flow, (hipStream_t)stream) : x16_grad_launch<bf16_t>(p, grad_flow, (hipStream_t)stream);
+    p.g_sign = g_scale;
+    return dtype == OFL_X16_HALF ? x16_grad_launch<half_t>(p, grad_flow, path, (hipStream_t)stream) : x16_grad_launch<bf16_t>(p, grad_flow, path, (hipStream_t)stream);
 }
 #else
-int g_warp_path = 0;   // ofl_set_option(OFL_OPT_WARP_PATH, .): 0 auto, 1 generic direct-gather kernel only, 2 (= auto), 3 / 4 staged with two tiles / one tile per block whatever the launch size (tests), 5 = auto but more than 3 channels as separate launches of 3 (tests: the channel-loop kernel against them), 6 = auto but the sheared rectangle instead of per-row extents (tests, A/B), 7 = auto but plain lean launches on four-tile row-table columns whatever the size (tests)
+int g_warp_path = kPathAuto;   // ofl_set_option(OFL_OPT_WARP_PATH, .): a WarpPath
 int g_warp_shear = 1;   // ofl_set_option(OFL_OPT_WARP_SHEAR, .)
 int g_splat_pass_images = 0;   // ofl_set_option(OFL_OPT_SPLAT_PASS_IMAGES, .): 0 = automatic (one pass unless the fallback accumulator of a pass would pass 2^31 floats)
 int g_splat_extra_lds = 0;   // ofl_set_option(OFL_OPT_SPLAT_EXTRA_LDS, .): bytes of dynamic LDS added to the diet kernel's launches (occupancy experiments: 28 672 -> two blocks per CU, 65 536 -> one)
 int g_splat_fallback_slots = 0;   // ofl_set_option(OFL_OPT_SPLAT_FALLBACK_SLOTS, .): 0 = automatic (1 GiB); tests use 1 to exercise the rounds
 
+// one launch of up to 3 channels on the kernel warp_choose() picked: the row-table and 64 x 16 column kernels through ofl_warp_wide.hip,
+// the others (32 x 16 tiles) here
 template <int NC>
-int launch_warp_lds(const WarpParams& p, unsigned grid, hipStream_t st) {
+int launch_warp_lds(const WarpParams& p, WarpChoice ch, hipStream_t st) {
+    if (ch.family == kWarpRows) return ofl_wide_launch_rows(&p, NC, ch.tiles, (void*)st);
+    if (ch.family == kWarpColumn && ch.wide) return ofl_wide_launch_column(&p, NC, (void*)st);
     const bool valid = p.valid != nullptr, add = p.addend != nullptr;
-    if (NC == 2 && p.src_b) {                              // (host: 2 channels, valid mask, no addend, no output flags)
-        if (kLdsT > 2 && g_warp_path != 3 && g_warp_path != 4) {   // large launches: columns of four tiles, lean when the promises hold
-            WarpParams q = p;
-            const unsigned gc = warp_geometry(q, kLdsTWQ * 4, kLdsT * kLdsTH);
-            constexpr int TT = kLdsT > 2 ? kLdsT : 3;
-            if (gc >= 6912u) {
-                if (warp_is_lean(q) && g_warp_path != 6) return ofl_wide_launch_column(&p, 2, 1, 0, 1, (void*)st);   // 64 x 16 tiles, per-row extents
-                if (warp_is_lean(q)) OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, true, false, false, NC == 2, float, float, false, false, true>), dim3(gc), dim3(kLdsNT), kLdsBytes, st, q);
-                else OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, true, false, false, NC == 2>), dim3(gc), dim3(kLdsNT), kLdsBytes, st, q);
-                return (int)hipGetLastError();
-            }
-        }
-        OFL_KLAUNCH((warp_bwd_lds_kernel<NC, true, false, false, NC == 2>), dim3(grid), dim3(kLdsNT), kLdsBytes, st, p);
-        return (int)hipGetLastError();
-    }
-    if (NC == 2 && p.dst_flags) {                          // (host: only with a valid mask)
-        if (kLdsT > 2 && valid && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4) {   // large lean launches: the row-table kernel keeps the flag by-product
-            WarpParams q = p;
-            if (warp_is_lean(q) && warp_geometry(q, kLdsTWQ * 4, kLdsT * kLdsTH) >= 6912u) return ofl_wide_launch_column(&p, 2, 1, add ? 1 : 0, 1, (void*)st);
-        }
-        if (add) OFL_KLAUNCH((warp_bwd_lds_kernel<NC, true, true, NC == 2>), dim3(grid), dim3(kLdsNT), kLdsBytes, st, p);
-        else OFL_KLAUNCH((warp_bwd_lds_kernel<NC, true, false, NC == 2>), dim3(grid), dim3(kLdsNT), kLdsBytes, st, p);
-        return (int)hipGetLastError();
-    }
-    // the fused composition (an addend): row tables where the launch is lean, else -- large launches only -- the four-tile column kernels
-    // (REUSE / lean twins: no scratch since round 5); small and forced-path launches fall through to the pair / one-tile kernels
-    if (kLdsT > 2 && add && NC == 2 && !p.flow_flags) {
-        WarpParams q = p;
-        const unsigned g = warp_geometry(q, kLdsTWQ * 4, kLdsT * kLdsTH);
-        // large launches of mode 3 proper and of another addend: 64 x 16 tiles with per-row extents (warp_bwd_rows_kernel<.., ADD>)
-        if (warp_is_lean(q) && g >= (g_warp_path == 0 && p.add_is_flow ? OFL_ROWS_T4_MIN : 6912u) && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4)
-            return ofl_wide_launch_column(&p, NC, valid ? 1 : 0, 1, 1, (void*)st);
-        if (p.add_is_flow && warp_is_lean(q) && g < OFL_ROWS_T4_MIN && g_warp_path == 0) {     // small mode 3
-            WarpParams q1 = p;
-            return ofl_wide_launch_rows_small(&p, 2, valid ? 1 : 0, 1, warp_geometry(q1, kLdsTWQ * 4, kLdsTH) < OFL_ROWS_T1_MAX ? 1 : 2, (void*)st);
-        }
-        // the four-tile column kernels below are for LARGE launches on the automatic path (small launches keep the pair /
-        // one-tile kernels further down -- half as many, twice as long blocks lose there -- and OFL_OPT_WARP_PATH 3 / 4 must reach them)
-        if (g >= 6912u && g_warp_path != 3 && g_warp_path != 4) {
-            if (p.add_is_flow) {                       // (mode 3 proper: the flow registers are the addend, REUSE)
-                if (warp_is_lean(q)) {
-                    if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, true, true, false, false, float, float, false, true, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-                    else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, false, true, false, false, float, float, false, true, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-                } else if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, true, true, false, false, float, float, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-                else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), 2, false, true, false, false, float, float, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-                return (int)hipGetLastError();
-            }
-            if (warp_is_lean(q)) {                     // (the addend is another flow: the outer `flow - (...)` of modes 1-2, Flow.combine's cells)
-                if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, true, true, false, false, float, float, false, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-                else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, false, true, false, false, float, float, false, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-                return (int)hipGetLastError();
-            }
-            if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, true, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-            else OFL_KLAUNCH((warp_bwd_lds_column_kernel<(kLdsT > 2 ? kLdsT : 3), NC, false, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q);
-            return (int)hipGetLastError();
-        }
-    }
-    // a plain warp (Flow.apply 't' of an image or a flow): columns of kLdsT tiles -- unless the launch is SMALL: a column block
-    // lives 4 tiles long, and with fewer than ~4.5 blocks per resident slot (256 CUs x 6) the chip idles behind the last
-    // ones.  Below that the pair kernel's twice-as-many, half-as-long blocks win: B = 1 / 2 / 4 / 6 at 1080p -4 / -15 / -7 /
-    // -5 %, B >= 8 the column kernel by 1-4 % (profiles/r4_small_batch_kernel_choice.txt)
-    constexpr unsigned kColumnMinGroups = 6912;
-    // ... and a TINY launch (fewer single tiles than that: a 1080p frame at B = 1 has 4 080) takes ONE tile per block: 2.7 short
-    // rounds of blocks instead of 1.3 long ones -- B = 1 1080p apply 21.7 -> 19.2 us, mode 3 20.6 -> 18.4 us; from B = 2 the
-    // pair kernel is level or ahead (profiles/r4_small_batch_kernel_choice.txt)
-    {
-        WarpParams q1 = p;
-        const unsigned g1 = warp_geometry(q1, kLdsTWQ * 4, kLdsTH);
-        if (g_warp_path == 7 && !add && warp_is_lean(q1)) return ofl_wide_launch_column(&p, NC, valid ? 1 : 0, 0, 1, (void*)st);   // (tests / experiments: four-tile columns with row tables whatever the size)
-        // small plain launches on the row-table kernel (1 tile per block for tiny ones, else 2): see ofl_wide_launch_rows_small
-        if (!add && !p.flow_flags && g_warp_path == 0 && warp_is_lean(q1)) {
-            WarpParams q4 = p;
-            const unsigned g4 = warp_geometry(q4, kLdsTWQ * 4, kLdsT * kLdsTH);
-            if (g4 < OFL_ROWS_T4_MIN) return ofl_wide_launch_rows_small(&p, NC, valid ? 1 : 0, 0, g1 < OFL_ROWS_T1_MAX ? 1 : 2, (void*)st);
-            if (g4 < kColumnMinGroups) return ofl_wide_launch_column(&p, NC, valid ? 1 : 0, 0, 1, (void*)st);      // (four tiles per block a little earlier than the rectangle's kernels: B = 6 at 1080p 76.5 -> 74.5 us)
-        }
-        if (g_warp_path == 4 || (g_warp_path != 3 && g1 < kColumnMinGroups)) {
-            if (warp_is_lean(q1) && valid) {            // (the lean twins of the two instantiations with a valid mask: BASELINE configs[1] is one of them)
-                if (add) OFL_KLAUNCH((warp_bwd_lds_column_kernel<1, NC, true, true, false, false, float, float, false, false, true>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q1);
-                else OFL_KLAUNCH((warp_bwd_lds_column_kernel<1, NC, true, false, false, false, float, float, false, false, true>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q1);
-                return (int)hipGetLastError();
-            }
-            if (valid && add) OFL_KLAUNCH((warp_bwd_lds_column_kernel<1, NC, true, true>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q1);
-            else if (valid) OFL_KLAUNCH((warp_bwd_lds_column_kernel<1, NC, true, false>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q1);
-            else if (add) OFL_KLAUNCH((warp_bwd_lds_column_kernel<1, NC, false, true>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q1);
-            else OFL_KLAUNCH((warp_bwd_lds_column_kernel<1, NC, false, false>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q1);
-            return (int)hipGetLastError();
-        }
-    }
     WarpParams q = p;
-    const unsigned g = (kLdsT > 2 && !add && !p.flow_flags) ? warp_geometry(q, kLdsTWQ * 4, kLdsT * kLdsTH) : 0u;
-    if (g >= kColumnMinGroups && g_warp_path != 3)
-        return ofl_wide_launch_column(&p, NC, valid ? 1 : 0, 0, g_warp_path != 6, (void*)st);    // 64 x 16 tiles: -1.9 % (see kLdsNT)
-#define OFL_LAUNCH_L(V, A)                                                                                       \
-    if (valid == V && add == A) {                                                                                \
-        OFL_KLAUNCH((warp_bwd_lds_kernel<NC, V, A>), dim3(grid), dim3(kLdsNT), kLdsBytes, st, p);          \
-        return (int)hipGetLastError();                                                                           \
+    const unsigned g = warp_geometry(q, kLdsTWQ * 4, ch.tiles * kLdsTH);
+#define OFL_COLUMN(...) OFL_KLAUNCH((warp_bwd_lds_column_kernel<__VA_ARGS__>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q)
+#define OFL_PAIR(...) OFL_KLAUNCH((warp_bwd_lds_kernel<__VA_ARGS__>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q)
+    switch (ch.family) {
+        case kWarpColumn:
+            if (ch.tiles == 1) {
+                if (ch.lean) OFL_WITH_BOOL(add, A, OFL_COLUMN(1, NC, true, A, false, false, float, float, false, false, true));      // (the lean twins: with a valid mask only)
+                else OFL_WITH_BOOL(valid, V, OFL_WITH_BOOL(add, A, OFL_COLUMN(1, NC, V, A)));
+            } else if (NC == 2 && p.src_b) {               // (host: 2 channels, valid mask, no addend, no output flags)
+                OFL_WITH_BOOL(ch.lean, LN, OFL_COLUMN(kLdsT, 2, true, false, false, NC == 2, float, float, false, false, LN));
+            } else if (p.add_is_flow) {                    // (mode 3 proper: the flow registers are the addend, REUSE)
+                OFL_WITH_BOOL(valid, V, OFL_WITH_BOOL(ch.lean, LN, OFL_COLUMN(kLdsT, 2, V, true, false, false, float, float, false, true, LN)));
+            } else {                                       // (the addend is another flow: the outer `flow - (...)` of modes 1-2, Flow.combine's cells)
+                OFL_WITH_BOOL(valid, V, OFL_WITH_BOOL(ch.lean, LN, OFL_COLUMN(kLdsT, NC, V, true, false, false, float, float, false, false, LN)));
+            }
+            break;
+        case kWarpPair:
+            if (NC == 2 && p.src_b) OFL_PAIR(NC, true, false, false, NC == 2);
+            else if (NC == 2 && p.dst_flags) OFL_WITH_BOOL(add, A, OFL_PAIR(NC, true, A, NC == 2));          // (host: only with a valid mask)
+            else OFL_WITH_BOOL(valid, V, OFL_WITH_BOOL(add, A, OFL_PAIR(NC, V, A)));
+            break;
+        default: return OFL_E_ARG;
     }
-    OFL_LAUNCH_L(false, false) OFL_LAUNCH_L(true, false) OFL_LAUNCH_L(false, true) OFL_LAUNCH_L(true, true)
-#undef OFL_LAUNCH_L
-    return OFL_E_ARG;
+#undef OFL_PAIR
+#undef OFL_COLUMN
+    return (int)hipGetLastError();
 }
 
-// 8-bit images: uint8 source planes, float or uint8 destination (no addend, no flag words)
+// 8-bit images: uint8 source planes, float or uint8 destination (no addend, no flag words), the pair kernel
 template <int NC, typename TD>
-int launch_warp_lds_u8(const WarpParams& p, unsigned grid, hipStream_t st) {
-    if (p.valid) OFL_KLAUNCH((warp_bwd_lds_kernel<NC, true, false, false, false, uint8_t, TD>), dim3(grid), dim3(kLdsNT), kLdsBytes, st, p);
-    else OFL_KLAUNCH((warp_bwd_lds_kernel<NC, false, false, false, false, uint8_t, TD>), dim3(grid), dim3(kLdsNT), kLdsBytes, st, p);
+int launch_warp_lds_u8(WarpParams& q, hipStream_t st) {
+    const unsigned g = warp_geometry(q, kLdsTWQ * 4, 2 * kLdsTH);
+    OFL_WITH_BOOL(q.valid != nullptr, V, OFL_KLAUNCH((warp_bwd_lds_kernel<NC, V, false, false, false, uint8_t, TD>), dim3(g), dim3(kLdsNT), kLdsBytes, st, q));
     return (int)hipGetLastError();
 }
 
@@ -4350,17 +4364,8 @@ void launch_flow_flags(const float* flow, int64_t flow_bs, const uint8_t* mask, 
 template <int CT>
 int launch_warp(const WarpParams& p, unsigned grid, hipStream_t st) {
     const bool valid = p.valid != nullptr, add = p.addend != nullptr, flags = p.flow_flags != nullptr;
-#define OFL_LAUNCH_W(V, A, F)                                                                  \
-    if (valid == V && add == A && flags == F) {                                                \
-        OFL_KLAUNCH((warp_bwd_kernel<CT, V, A, F>), dim3(grid), dim3(256), 0, st, p);    \
-        return (int)hipGetLastError();                                                         \
-    }
-    OFL_LAUNCH_W(false, false, false) OFL_LAUNCH_W(true, false, false)
-    OFL_LAUNCH_W(false, true, false) OFL_LAUNCH_W(true, true, false)
-    OFL_LAUNCH_W(false, false, true) OFL_LAUNCH_W(true, false, true)
-    OFL_LAUNCH_W(false, true, true) OFL_LAUNCH_W(true, true, true)
-#undef OFL_LAUNCH_W
-    return OFL_E_ARG;
+    OFL_WITH_BOOL(valid, V, OFL_WITH_BOOL(add, A, OFL_WITH_BOOL(flags, F, OFL_KLAUNCH((warp_bwd_kernel<CT, V, A, F>), dim3(grid), dim3(256), 0, st, p))));
+    return (int)hipGetLastError();
 }
 
 
@@ -4407,52 +4412,32 @@ int launch_splat_gather_half(const GatherParams& gp, unsigned grid, hipStream_t 
 
 }  // namespace
 
-// The gradient of the backward warp with respect to its FLOW on the staged column kernel (called by ofl_warp_bwd_grad_f32 in
+// The gradient of the backward warp with respect to its FLOW on the staged kernels (called by ofl_warp_bwd_grad_f32 in
 // ofl_aux_kernels.hip; not exported).  OFL_E_UNSUPPORTED: the frame is not eligible (the caller's one-pixel-per-lane kernel takes it).
 int ofl_internal_warp_grad_flow_lds(const float* flow, int64_t flow_bs, float flow_sign, const float* src, int64_t src_bs,
                                     const float* grad_out, float g_scale, float* grad_flow, int32_t n, int32_t c, int32_t h, int32_t w,
                                     hipStream_t st) {
-    const bool lds_ok = g_warp_path != 1 && c >= 1 && c <= 3 && w >= 4 && h >= 2 && w < 32760 && h < 32760 && (int64_t)h * w < (1ll << 24);
-    if (!lds_ok || kLdsT <= 2) return OFL_E_UNSUPPORTED;
-    if ((int64_t)((w + 31) / 32) * ((h + 15) / 16) * n >= (1ll << 31)) return OFL_E_SHAPE;
-    WarpParams p = {};
-    p.flow = flow; p.flow_bs = flow_bs; p.src = src; p.src_bs = src_bs;
-    p.addend = grad_out; p.addend_bs = (int64_t)c * h * w;           // (the column kernel fetches the upstream gradient where mode 3 fetches its addend)
+    if (!(path_staged(g_warp_path) && c >= 1 && c <= 3 && warp_frame_staged(h, w))) return OFL_E_UNSUPPORTED;
+    if (warp_tiles_overflow(n, h, w)) return OFL_E_SHAPE;
+    WarpParams p;
+    warp_params_init(p, n, c, h, w, flow, flow_bs, flow_sign);
+    p.src = src; p.src_bs = src_bs;
+    p.addend = grad_out; p.addend_bs = (int64_t)c * h * w;           // (the kernels fetch the upstream gradient where mode 3 fetches its addend)
     p.dst = grad_flow; p.dst_bs = (int64_t)2 * h * w;
-    p.n = n; p.c = c; p.h = h; p.w = w;
-    p.flow_sign = flow_sign; p.a_sign = 1.0f; p.g_sign = g_scale; p.round_mode = OFL_ROUND_NONE;
-    p.wm1 = (float)(w - 1); p.hm1 = (float)(h - 1);
-    p.half_wm1 = p.wm1 / 2.0f; p.half_hm1 = p.hm1 / 2.0f;
-    p.rcp_wm1 = 1.0f / p.wm1; p.rcp_hm1 = 1.0f / p.hm1;
-    p.lds_bytes = kLdsBytes;
-    p.shear = (g_warp_shear && (int64_t)h + 4 * (int64_t)w + 8 < 32760) ? 1 : 0;
+    p.g_sign = g_scale;
+    const WarpChoice ch = warp_choose(p, kWarpGrad, g_warp_path);
+    if (ch.family == kWarpRows) {                                    // 64 x 16 tiles, per-row extents
+        const int rr = ofl_wide_launch_rows_grad(&p, c, ch.tiles, (void*)st);
+        if (rr != OFL_E_UNSUPPORTED) return rr;
+    }
     const unsigned g = warp_geometry(p, kLdsTWQ * 4, kLdsT * kLdsTH);
-    constexpr int TT = kLdsT > 2 ? kLdsT : 3;
-    if (warp_is_lean(p) && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4) {   // 64 x 16 tiles, per-row extents
-        if (g >= (g_warp_path == 0 ? OFL_ROWS_T4_MIN : 6912u) || g_warp_path == 7) {
-            const int rr = ofl_wide_launch_rows_grad(&p, c, OFL_ROWS_T, (void*)st);
-            if (rr != OFL_E_UNSUPPORTED) return rr;
-        }
-        if (g_warp_path == 0) {            // small launches (the shapes training runs at): one tile per block for tiny ones, else two
-            WarpParams q1 = p;
-            const int rr = ofl_wide_launch_rows_grad(&p, c, warp_geometry(q1, kLdsTWQ * 4, kLdsTH) < OFL_ROWS_T1_MAX ? 1 : 2, (void*)st);
-            if (rr != OFL_E_UNSUPPORTED) return rr;
-        }
-    }
-    switch (c) {
-        case 1: OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 1, false, false, false, false, float, float, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, p); break;
-        case 2: OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, false, false, false, false, float, float, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, p); break;
-        default: OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 3, false, false, false, false, float, float, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, p); break;
-    }
+    OFL_WITH_NC(c, NC, OFL_KLAUNCH((warp_bwd_lds_column_kernel<kLdsT, NC, false, false, false, false, float, float, true>), dim3(g), dim3(kLdsNT), kLdsBytes, st, p));
     return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
-extern "C" {
-
-}  // extern "C"
 const void* g_ofl_last_kernel = nullptr;
 int ofl_warp_path_option(void) { return g_warp_path; }
 int ofl_warp_shear_option(void) { return g_warp_shear; }
@@ -4464,7 +4449,7 @@ __attribute__((visibility("default"))) const char* ofl_last_kernel_name(void) {
 __attribute__((visibility("default"))) int ofl_version(void) { return 36; }   // 36: ofl_matrix_workspace_bytes / ofl_matrix_fit_f64 (ofl_matrix.hip); 35: OFL_OPT_SPLAT_PATH retired; 34: ofl_visualise_workspace_ints / ofl_visualise_range_f32 / ofl_visualise_u8 (ofl_visualise.hip); 33: the gather splat's diet kernel (ofl_splat_gather.hip), OFL_OPT_SPLAT_PATH / OFL_OPT_SPLAT_EXTRA_LDS, ofl_splat_gather_info; 32: OFL_OPT_WARP_PATH value 7 (four-tile row-table columns whatever the size); row tables for small launches, the other flow-level warps, fp16 / uint8 sources, the gradient-wrt-flow pass; 31: OFL_OPT_WARP_PATH value 6 (the sheared rectangle instead of per-row extents: warp_bwd_rows_kernel is the default for large lean launches); 30: OFL_OPT_WARP_PATH value 5 (more than 3 channels as launches of 3; the default is ONE launch that loops over the channels); 29: ofl_splat_tile_geometry (64 x 16 destination tiles); 28: ofl_resize_bilinear_f32; 27: ofl_warp_valid_f32 (ofl_aux_kernels.hip); 26: bounded fallback accumulator of the gather splat (ofl_splat_tiled_fallback_images); 25: ofl_flow_flags_host with sharded arrival counters and {serial, word} pairs, ofl_flow_from_matrix_f32; 24: ofl_flow_flags_host (+ ofl_host_words_alloc / _free); 23: scratch argument of ofl_splat_grad_f32; 22: ofl_splat_sum_f32; 21: ofl_flag_words_or_i32, splat workspace without the fold-tile list; 20: fp16-stored flows read directly (ofl_splat_tiled_f16, ofl_warp_bwd_h_f32, flags-only ofl_flow_from_f16); 19: gather-formulation splat (workspace layout), ofl_warp_bwd_win_f32 / ofl_splat_tiled_win_f32 (padded apply); 18: ofl_aux_kernels.hip (backward passes, point sampler, extents); 13: dst_flags in ofl_warp_bwd_f32 / ofl_splat_tiled_f32, fixed-address splat queues; 14: data_b; 15: src_b; 16: ofl_warp_bwd_u8; 17: ofl_flow_from_f16
 
 __attribute__((visibility("default"))) int ofl_set_option(int32_t key, int32_t value) {
-    if (key == OFL_OPT_WARP_PATH && value >= 0 && value <= 7) { g_warp_path = value; return OFL_OK; }
+    if (key == OFL_OPT_WARP_PATH && value >= kPathAuto && value <= kPathRowColumns) { g_warp_path = value; return OFL_OK; }
     if (key == OFL_OPT_WARP_SHEAR && (value == 0 || value == 1)) { g_warp_shear = value; return OFL_OK; }
     if (key == OFL_OPT_SPLAT_PASS_IMAGES && value >= 0) { g_splat_pass_images = value; return OFL_OK; }
     if (key == OFL_OPT_SPLAT_FALLBACK_SLOTS && value >= 0) { g_splat_fallback_slots = value; return OFL_OK; }
@@ -4486,30 +4471,23 @@ static int warp_bwd_impl(
     if (round_mode < 0 || round_mode > 2) return OFL_E_ARG;
     if (!(flow_sign == 1.0f || flow_sign == -1.0f)) return OFL_E_ARG;
     WarpParams p;
-    p.flow = flow; p.flow_bs = flow_bs; p.src = src; p.src_bs = src_bs;
-    p.src_b = nullptr; p.src_b_bs = 0;
+    warp_params_init(p, n, c, h, w, flow, flow_bs, flow_sign);
+    p.src = src; p.src_bs = src_bs;
     p.src_mask = src_mask; p.src_mask_bs = src_mask_bs; p.flow_mask = flow_mask; p.flow_mask_bs = flow_mask_bs;
     p.addend = addend; p.addend_bs = addend_bs; p.dst = dst; p.valid = valid;
-    p.flow_flags = flow_flags; p.src_flags = src_flags; p.dst_flags = nullptr;
-    p.n = n; p.c = c; p.h = h; p.w = w;
-    p.flow_sign = flow_sign; p.a_sign = a_sign; p.g_sign = g_sign; p.round_mode = round_mode;
-    p.wm1 = (float)(w - 1); p.hm1 = (float)(h - 1);
-    p.half_wm1 = p.wm1 / 2.0f; p.half_hm1 = p.hm1 / 2.0f;
-    p.rcp_wm1 = 1.0f / p.wm1; p.rcp_hm1 = 1.0f / p.hm1;
-    p.lds_bytes = kLdsBytes;
-    p.shear = (g_warp_shear && (int64_t)h + 4 * (int64_t)w + 8 < 32760) ? 1 : 0;   // sheared rows stay within 16 bits (|slope| <= 16 rows per chunk column)
+    p.flow_flags = flow_flags; p.src_flags = src_flags;
+    p.a_sign = a_sign; p.g_sign = g_sign; p.round_mode = round_mode;
     p.add_is_flow = (addend != nullptr && addend == flow && addend_bs == flow_bs && c == 2) ? 1 : 0;
     p.dst_bs = (int64_t)c * h * w;
     p.fh = fh; p.fw = fw; p.foy = foy; p.fox = fox;
     hipStream_t st = (hipStream_t)stream;
-    if ((int64_t)((w + 31) / 32) * ((h + 15) / 16) * n >= (1ll << 31)) return OFL_E_SHAPE;
+    if (warp_tiles_overflow(n, h, w)) return OFL_E_SHAPE;
     if (dst_flags) {
         hipError_t e = hipMemsetAsync(dst_flags, 0, (size_t)n * sizeof(int32_t), st);
         if (e != hipSuccess) return (int)e;
     }
-    // LDS-staged fast path: <= 3 channels, at least one whole 4-pixel group per row, 16-bit box coordinates (any width:
-    // 16-byte accesses at 4-byte alignment, mask bytes at any alignment)
-    const bool lds_ok = g_warp_path != 1 && w >= 4 && h >= 2 && w < 32760 && h < 32760 && (int64_t)h * w < (1ll << 24) && fw == 0;
+    // LDS-staged fast path (not for a flow window); more than 3 channels in groups of 3 or in the channel loop
+    const bool lds_ok = warp_staged(p, g_warp_path);
     if (src_b) {   // only the staged 2-channel kernel with a valid mask subtracts on the fly: anything else is the caller's job
         if (!(lds_ok && c == 2 && valid && !addend && !dst_flags && !flow_flags)) return OFL_E_UNSUPPORTED;
         p.src_b = src_b; p.src_b_bs = src_b_bs;
@@ -4521,21 +4499,12 @@ static int warp_bwd_impl(
             p.src_flags = nullptr;
         }
         p.dst_flags = dst_flags;                                             // a by-product of the staged kernel (c == 2: one group)
-        const unsigned g = warp_geometry(p, kLdsTWQ * 4, 2 * kLdsTH);
-        // more than 3 channels of a plain warp: ONE launch that walks the channels inside the block (warp_bwd_lds_chan_kernel)
-        // (with the valid area wanted the first group is 3 channels + the mask plane: below 7 channels two launches of 3 are as good or better)
-        if (c >= (valid ? 7 : 4) && (w & 3) == 0 && !addend && !src_b && !dst_flags && g_warp_path != 5) {
+        const WarpChoice whole = warp_choose(p, kWarpPlain, g_warp_path);
+        if (whole.family == kWarpChan || whole.family == kWarpChanRows) {    // ONE launch that walks the channels inside the block
+            if (whole.wide) return ofl_wide_launch_chan(&p, whole.family == kWarpChanRows ? 1 : 0, (void*)st);
             WarpParams q = p;
             const unsigned g1 = warp_geometry(q, kLdsTWQ * 4, kLdsTH);
-            // 64 x 16 tiles for large launches -- and, with per-row extents (lean, two channel groups or more), for EVERY size: B = 1 C = 64
-            // 0.355 -> 0.255 ms, C = 16 0.071 -> 0.054 ms against the 32 x 16 rectangle version (tools/bench_chan.py --batch 1)
-            const bool rows_chan = g_warp_path != 6 && c >= 7 && warp_is_lean(q);
-            if (g1 >= OFL_WARP_CHAN_WIDE_MIN || rows_chan) return ofl_wide_launch_chan(&p, p.valid ? 1 : 0, rows_chan ? 1 : 0, (void*)st);   // (row extents from two channel groups on: with one group their set-up is not amortised -- C = 4: 0.148 against 0.138 ms)
-            if (warp_is_lean(q)) {
-                if (q.valid) OFL_KLAUNCH((warp_bwd_lds_chan_kernel<true, true>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q);
-                else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false, true>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q);
-            } else if (q.valid) OFL_KLAUNCH((warp_bwd_lds_chan_kernel<true>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q);
-            else OFL_KLAUNCH((warp_bwd_lds_chan_kernel<false>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q);
+            OFL_WITH_BOOL(q.valid != nullptr, V, OFL_WITH_BOOL(whole.lean, LN, OFL_KLAUNCH((warp_bwd_lds_chan_kernel<V, LN>), dim3(g1), dim3(kLdsNT), kLdsBytes, st, q)));
             return (int)hipGetLastError();
         }
         // otherwise groups of 3 (the staged box holds 3 channels + the mask channel); the valid mask and the
@@ -4547,11 +4516,8 @@ static int warp_bwd_impl(
             q.src = src + c0 * hw; q.dst = dst + c0 * hw;                 // (batch strides stay: planes of one image are contiguous)
             if (addend) q.addend = addend + c0 * hw;
             if (c0 > 0) { q.valid = nullptr; q.flow_flags = nullptr; q.src_mask = nullptr; }
-            switch (nc) {
-                case 1: rc = launch_warp_lds<1>(q, g, st); break;
-                case 2: rc = launch_warp_lds<2>(q, g, st); break;
-                default: rc = launch_warp_lds<3>(q, g, st); break;
-            }
+            const WarpChoice ch = whole.family == kWarpSplit ? warp_choose(q, kWarpPlain, g_warp_path) : whole;
+            OFL_WITH_NC(nc, NC, rc = launch_warp_lds<NC>(q, ch, st));
             if (rc) return rc;
         }
         return OFL_OK;
@@ -4600,23 +4566,17 @@ __attribute__((visibility("default"))) int ofl_warp_bwd_u8(
     if (round_mode < 0 || round_mode > 2) return OFL_E_ARG;
     if (dst_is_u8 && round_mode != OFL_ROUND_U8) return OFL_E_ARG;       // bytes only hold rounded, clamped values
     if (!(flow_sign == 1.0f || flow_sign == -1.0f)) return OFL_E_ARG;
-    if ((int64_t)((w + 31) / 32) * ((h + 15) / 16) * n >= (1ll << 31)) return OFL_E_SHAPE;
-    if (!(g_warp_path != 1 && w >= 4 && h >= 2 && w < 32760 && h < 32760)) return OFL_E_UNSUPPORTED;   // staged kernel only
-    WarpParams p = {};
-    p.flow = flow; p.flow_bs = flow_bs; p.src_bs = src_bs;
+    if (warp_tiles_overflow(n, h, w)) return OFL_E_SHAPE;
+    if (!(path_staged(g_warp_path) && warp_frame_staged(h, w))) return OFL_E_UNSUPPORTED;   // staged kernel only
+    WarpParams p;
+    warp_params_init(p, n, c, h, w, flow, flow_bs, flow_sign);
+    p.src_bs = src_bs;
     p.src_mask = src_mask; p.src_mask_bs = src_mask_bs; p.flow_mask = flow_mask; p.flow_mask_bs = flow_mask_bs;
     p.valid = valid;
-    p.n = n; p.c = c; p.h = h; p.w = w;
-    p.flow_sign = flow_sign; p.a_sign = 1.0f; p.g_sign = 1.0f; p.round_mode = round_mode;
-    p.wm1 = (float)(w - 1); p.hm1 = (float)(h - 1);
-    p.half_wm1 = p.wm1 / 2.0f; p.half_hm1 = p.hm1 / 2.0f;
-    p.rcp_wm1 = 1.0f / p.wm1; p.rcp_hm1 = 1.0f / p.hm1;
-    p.lds_bytes = kLdsBytes;
-    p.shear = (g_warp_shear && (int64_t)h + 4 * (int64_t)w + 8 < 32760) ? 1 : 0;
+    p.round_mode = round_mode;
     p.dst_bs = (int64_t)c * h * w;
     hipStream_t st = (hipStream_t)stream;
     const int64_t hw = (int64_t)h * w;
-    const unsigned g = warp_geometry(p, kLdsTWQ * 4, 2 * kLdsTH);
     for (int32_t c0 = 0; c0 < c; c0 += 3) {                               // channel groups of 3, as ofl_warp_bwd_f32
         const int32_t nc = (c - c0) < 3 ? (c - c0) : 3;
         WarpParams q = p;
@@ -4624,23 +4584,13 @@ __attribute__((visibility("default"))) int ofl_warp_bwd_u8(
         q.src = reinterpret_cast<const float*>(src + c0 * hw);             // (the uint8 kernels re-read these as byte pointers)
         q.dst = dst_is_u8 ? reinterpret_cast<float*>(static_cast<uint8_t*>(dst) + c0 * hw) : static_cast<float*>(dst) + c0 * hw;
         if (c0 > 0) { q.valid = nullptr; q.src_mask = nullptr; }
-        if ((nc == 1 || nc == 3) && (w & 3) == 0 && kLdsT > 2 && g_warp_path != 6 && g_warp_path != 3 && g_warp_path != 4) {
-            WarpParams qg = q;                           // large launches: 64 x 16 tiles, per-row extents
-            if (warp_geometry(qg, kLdsTWQ * 4, kLdsT * kLdsTH) >= 6912u) { rc = ofl_wide_launch_rows_u8(&q, nc, dst_is_u8, stream); if (rc == OFL_OK) continue; if (rc != OFL_E_UNSUPPORTED) return rc; }
+        if (warp_choose(q, kWarpU8, g_warp_path).family == kWarpRows) {      // large launches: 64 x 16 tiles, per-row extents
+            rc = ofl_wide_launch_rows_u8(&q, nc, dst_is_u8, stream);
+            if (rc == OFL_OK) continue;
+            if (rc != OFL_E_UNSUPPORTED) return rc;
         }
-        if (dst_is_u8) {
-            switch (nc) {
-                case 1: rc = launch_warp_lds_u8<1, uint8_t>(q, g, st); break;
-                case 2: rc = launch_warp_lds_u8<2, uint8_t>(q, g, st); break;
-                default: rc = launch_warp_lds_u8<3, uint8_t>(q, g, st); break;
-            }
-        } else {
-            switch (nc) {
-                case 1: rc = launch_warp_lds_u8<1, float>(q, g, st); break;
-                case 2: rc = launch_warp_lds_u8<2, float>(q, g, st); break;
-                default: rc = launch_warp_lds_u8<3, float>(q, g, st); break;
-            }
-        }
+        if (dst_is_u8) OFL_WITH_NC(nc, NC, rc = launch_warp_lds_u8<NC, uint8_t>(q, st));
+        else OFL_WITH_NC(nc, NC, rc = launch_warp_lds_u8<NC, float>(q, st));
         if (rc) return rc;
     }
     return OFL_OK;
@@ -4656,43 +4606,27 @@ __attribute__((visibility("default"))) int ofl_warp_bwd_h_f32(
     int rc = check_dims(n, 2, h, w, false);
     if (rc) return rc;
     if (!(flow_sign == 1.0f || flow_sign == -1.0f)) return OFL_E_ARG;
-    if ((int64_t)((w + 31) / 32) * ((h + 15) / 16) * n >= (1ll << 31)) return OFL_E_SHAPE;
-    if (!(g_warp_path != 1 && w >= 4 && h >= 2 && w < 32760 && h < 32760 && (int64_t)h * w < (1ll << 24))) return OFL_E_UNSUPPORTED;
-    WarpParams p = {};
-    p.flow = flow; p.flow_bs = flow_bs; p.src = static_cast<const float*>(src_f16); p.src_bs = src_bs;
+    if (warp_tiles_overflow(n, h, w)) return OFL_E_SHAPE;
+    if (!(path_staged(g_warp_path) && warp_frame_staged(h, w))) return OFL_E_UNSUPPORTED;
+    WarpParams p;
+    warp_params_init(p, n, 2, h, w, flow, flow_bs, flow_sign);
+    p.src = static_cast<const float*>(src_f16); p.src_bs = src_bs;
     p.src_b = src_b; p.src_b_bs = src_b_bs;
     p.src_mask = src_mask; p.src_mask_bs = src_mask_bs; p.flow_mask = flow_mask; p.flow_mask_bs = flow_mask_bs;
     p.dst = dst; p.valid = valid;
-    p.n = n; p.c = 2; p.h = h; p.w = w;
-    p.flow_sign = flow_sign; p.a_sign = 1.0f; p.g_sign = 1.0f; p.round_mode = OFL_ROUND_NONE;
-    p.wm1 = (float)(w - 1); p.hm1 = (float)(h - 1);
-    p.half_wm1 = p.wm1 / 2.0f; p.half_hm1 = p.hm1 / 2.0f;
-    p.rcp_wm1 = 1.0f / p.wm1; p.rcp_hm1 = 1.0f / p.hm1;
-    p.lds_bytes = kLdsBytes;
-    p.shear = (g_warp_shear && (int64_t)h + 4 * (int64_t)w + 8 < 32760) ? 1 : 0;
     p.dst_bs = (int64_t)2 * h * w;
     hipStream_t st = (hipStream_t)stream;
-    // large launches: columns of four tiles (round 5: every wait of that pipeline is counted, see lds_store), lean when the promises hold
-    if (kLdsT > 2 && g_warp_path != 3 && g_warp_path != 4) {
-        WarpParams q = p;
-        const unsigned gc = warp_geometry(q, kLdsTWQ * 4, kLdsT * kLdsTH);
-        constexpr int TT = kLdsT > 2 ? kLdsT : 3;
-        if (gc >= 6912u) {
-            const bool lean = warp_is_lean(q);
-            if (lean && g_warp_path != 6) {                                                  // 64 x 16 tiles, per-row extents
-                const int rr = ofl_wide_launch_rows_h(&p, stream);
-                if (rr != OFL_E_UNSUPPORTED) return rr;                                                            // (a launch it declines falls through to the column kernel)
-            }
-            if (src_b) { if (lean) OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, true, false, false, true, _Float16, float, false, false, true>), dim3(gc), dim3(kLdsNT), kLdsBytes, st, q);
-                         else OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, true, false, false, true, _Float16, float>), dim3(gc), dim3(kLdsNT), kLdsBytes, st, q); }
-            else { if (lean) OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, true, false, false, false, _Float16, float, false, false, true>), dim3(gc), dim3(kLdsNT), kLdsBytes, st, q);
-                   else OFL_KLAUNCH((warp_bwd_lds_column_kernel<TT, 2, true, false, false, false, _Float16, float>), dim3(gc), dim3(kLdsNT), kLdsBytes, st, q); }
-            return (int)hipGetLastError();
-        }
+    const WarpChoice ch = warp_choose(p, kWarpHalfSrc, g_warp_path);
+    if (ch.family == kWarpRows) {                                                                // 64 x 16 tiles, per-row extents
+        const int rr = ofl_wide_launch_rows_h(&p, stream);
+        if (rr != OFL_E_UNSUPPORTED) return rr;                                                  // (a launch it declines falls through to the column kernel)
     }
-    const unsigned g = warp_geometry(p, kLdsTWQ * 4, 2 * kLdsTH);
-    if (src_b) OFL_KLAUNCH((warp_bwd_lds_kernel<2, true, false, false, true, _Float16, float>), dim3(g), dim3(kLdsNT), kLdsBytes, st, p);
-    else OFL_KLAUNCH((warp_bwd_lds_kernel<2, true, false, false, false, _Float16, float>), dim3(g), dim3(kLdsNT), kLdsBytes, st, p);
+    // large launches: columns of four tiles (round 5: every wait of that pipeline is counted, see lds_store), lean when the promises hold
+    const bool pair = ch.family == kWarpPair, lean = warp_is_lean(p);
+    const unsigned g = warp_geometry(p, kLdsTWQ * 4, (pair ? 2 : kLdsT) * kLdsTH);
+    if (pair) OFL_WITH_BOOL(src_b != nullptr, SB, OFL_KLAUNCH((warp_bwd_lds_kernel<2, true, false, false, SB, _Float16, float>), dim3(g), dim3(kLdsNT), kLdsBytes, st, p));
+    else OFL_WITH_BOOL(src_b != nullptr, SB, OFL_WITH_BOOL(lean, LN,
+        OFL_KLAUNCH((warp_bwd_lds_column_kernel<kLdsT, 2, true, false, false, SB, _Float16, float, false, false, LN>), dim3(g), dim3(kLdsNT), kLdsBytes, st, p)));
     return (int)hipGetLastError();
 }
 

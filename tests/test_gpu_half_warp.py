@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 DTYPES = [torch.bfloat16, torch.float16]
 SEEN = set()          # demangled names of the 16-bit kernels the cases of this file reached
 
-# every instantiation x16_launch / x16_launch_group (ofl_kernels.hip, OFL_X16_TU) can pick, as (family, tiles per block, planes, VALID)
+# every instantiation warp_choose() can pick for x16_launch / x16_launch_group (ofl_kernels.hip, OFL_X16_TU), as (family, tiles per block, planes, VALID)
 ROWS = [("rows", t, nc, v) for t in (1, 2, 4) for nc in (1, 2, 3) for v in (True, False)]            # W % 4 == 0: row tables
 COLUMN = [("column", t, nc, v) for t in (1, 4) for nc in (1, 2, 3) for v in (True, False)]           # other widths: one tile / four-tile columns
 PAIR = [("pair", 2, nc, v) for nc in (1, 2, 3) for v in (True, False)]                               # ... and the two-tile kernel between them
