@@ -801,6 +801,40 @@ int ofl_decode_kitti(const uint8_t* raw, int64_t raw_bs, float* vecs, uint8_t* m
 int ofl_decode_flo(const float* raw, int64_t raw_bs, const uint8_t* grey, int64_t grey_bs, float* vecs, uint8_t* mask, int32_t* flags,
                    int32_t n, int32_t h, int32_t w, void* stream);
 
+/*
+ * Scoring an estimated flow against a ground truth (ofl_metrics.hip): Flow.error_stats / epe_map / epe.  An extension: the
+ * reference has no such function.  Per pixel, every step fp32 with one rounding per operation: du = u - ug, dv = v - vg,
+ * e = sqrt(du du + dv dv), g = sqrt(ug ug + vg vg), both roots correctly rounded; a pixel counts where both masks are True (a NULL mask
+ * is all True).  est / gt [*,2,H,W] fp32 (half = 0) or fp16 (1: up-converted in registers, exact), batch strides in elements; masks
+ * [*,H,W] bytes.  n <= 65535, h * w < 2^31.
+ *
+ * ofl_flow_error_workspace_bytes(n, h, w): bytes of the workspace of ofl_flow_error_f64 (8-byte aligned; every word the second launch
+ *   reads is written by the first: nothing to clear), or OFL_E_SHAPE.
+ *
+ * ofl_flow_error_f64: records float64 [n, OFL_FLOW_ERROR_RECORD], per image over its valid pixels
+ *     [0] count   [1] sum e   [2] max e (0 without a valid pixel)   [3 .. 6] pixels with e > t_k, k < n_thresholds (strict; 0 <=
+ *     n_thresholds <= 4, t_k finite and >= 0, else OFL_E_ARG)   [7] pixels with e > 3 and e > 0.05f * g (KITTI's Fl outliers, the product
+ *     in fp32)   [8 .. 10] pixels with g in [0, 10), [10, 40), [40, inf)   [11 .. 13] sum e of those   [14], [15] 0.
+ *   Counts are exact (integers up to the record).  Sums are float64 sums of the fp32 e in a fixed order -- a lane's pixels ascending,
+ *   the lanes of a wave by a butterfly, the waves and then the blocks of an image in index order -- and the number of blocks depends on
+ *   h * w only: no float atomics, an image's record has the same bits in any batch and on any run.  epe_map (optional) fp32 [n,h,w]: e,
+ *   0 where not valid.  Two launches: ofl_last_kernel_name() then names flow_error_finish_kernel.
+ *
+ * ofl_flow_epe_grad_f32: the backward of the per-image mean of e.  scale fp32 [n] DEVICE memory (the upstream gradient / count);
+ *   grad_est and / or grad_gt fp32 [n,2,h,w] (one may be NULL, not both): grad_est = the float64 quotient (scale du) / sqrt(du du + dv dv)
+ *   of the fp32 differences, rounded once to fp32, where the pixel is valid and the fp32 e is > 0; 0 elsewhere (the subgradient torch's
+ *   norm takes at 0); grad_gt = -grad_est.  A scale that is not finite (count 0) meets no valid pixel: that image's gradient is 0.
+ */
+#define OFL_FLOW_ERROR_RECORD 16
+int64_t ofl_flow_error_workspace_bytes(int32_t n, int32_t h, int32_t w);
+int ofl_flow_error_f64(const void* est, int64_t est_bs, int32_t est_half, const void* gt, int64_t gt_bs, int32_t gt_half,
+                       const uint8_t* est_mask, int64_t est_mask_bs, const uint8_t* gt_mask, int64_t gt_mask_bs, int32_t n_thresholds,
+                       float t0, float t1, float t2, float t3, void* workspace, float* epe_map, double* records,
+                       int32_t n, int32_t h, int32_t w, void* stream);
+int ofl_flow_epe_grad_f32(const void* est, int64_t est_bs, int32_t est_half, const void* gt, int64_t gt_bs, int32_t gt_half,
+                          const uint8_t* est_mask, int64_t est_mask_bs, const uint8_t* gt_mask, int64_t gt_mask_bs, const float* scale,
+                          float* grad_est, float* grad_gt, int32_t n, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,3 +209,25 @@ def sample_pts(flow, pts):
     if _native._wants_grad(flow, pts):
         return SamplePtsFn.apply(flow, pts)
     return _native.sample_pts(flow, pts)
+
+
+class EpeFn(torch.autograd.Function):
+    """epe[n] = mean over the valid pixels of |est - gt|   (Flow.epe): fp32, rounded once from the float64 quotient of
+    the kernel's sum and count; NaN for an image without a valid pixel, whose gradient is 0."""
+
+    @staticmethod
+    def forward(ctx, est, gt, est_mask, gt_mask):
+        rec, _ = _native.flow_error(est.detach(), gt.detach(), est_mask, gt_mask, (), False)
+        ctx.save_for_backward(est, gt, rec)
+        ctx.masks = (est_mask, gt_mask)
+        return (rec[:, 1] / rec[:, 0]).to(torch.float32)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        est, gt, rec = ctx.saved_tensors
+        need_est, need_gt = ctx.needs_input_grad[:2]
+        scale = (g.to(rec.device, torch.float64) / rec[:, 0]).to(torch.float32)          # on the device: nothing is read back
+        g_est, g_gt = _native.flow_epe_grad(est.detach(), gt.detach(), ctx.masks[0], ctx.masks[1], scale, want_est=bool(need_est),
+                                            want_gt=bool(need_gt))
+        return (_reduce_to(g_est, est) if need_est else None), (_reduce_to(g_gt, gt) if need_gt else None), None, None

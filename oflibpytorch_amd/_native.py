@@ -34,7 +34,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_mesh_workspace_ints", "ofl_mesh_plan", "ofl_mesh_apply", "ofl_mesh_points",
             "ofl_warp_bwd_x16", "ofl_warp_bwd_grad_x16", "ofl_splat_sum_x16", "ofl_warp_bwd_nhwc",
             "ofl_warp_bwd_grad_nhwc", "ofl_nhwc_to_planes", "ofl_planes_to_nhwc",
-            "ofl_png_unfilter", "ofl_png_grey8", "ofl_decode_kitti", "ofl_decode_flo")
+            "ofl_png_unfilter", "ofl_png_grey8", "ofl_decode_kitti", "ofl_decode_flo",
+            "ofl_flow_error_workspace_bytes", "ofl_flow_error_f64", "ofl_flow_epe_grad_f32")
 _lib = None
 _load_lock = threading.RLock()
 
@@ -142,11 +143,15 @@ def _load_library_locked(path: str = None):
     lib.ofl_png_grey8.argtypes = [p, i64, i32, i32, i32, i32, p, i32, p, i64]
     lib.ofl_decode_kitti.argtypes = [p, i64, p, p, p, i32, i32, i32, p]
     lib.ofl_decode_flo.argtypes = [p, i64, p, i64, p, p, p, i32, i32, i32, p]
+    lib.ofl_flow_error_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.ofl_flow_error_f64.argtypes = [p, i64, i32, p, i64, i32, p, i64, p, i64, i32, f32, f32, f32, f32, p, p, p, i32, i32, i32, p]
+    lib.ofl_flow_epe_grad_f32.argtypes = [p, i64, i32, p, i64, i32, p, i64, p, i64, p, p, p, i32, i32, i32, p]
     for name in _SYMBOLS:
         getattr(lib, name).restype = ctypes.c_int
     lib.ofl_arrows_workspace_ints.restype = ctypes.c_int64
     lib.ofl_mesh_workspace_ints.restype = ctypes.c_int64
     lib.ofl_matrix_workspace_bytes.restype = ctypes.c_int64
+    lib.ofl_flow_error_workspace_bytes.restype = ctypes.c_int64
     lib.ofl_splat_tiled_workspace_ints.restype = ctypes.c_int64
     lib.ofl_visualise_workspace_ints.restype = ctypes.c_int64
     lib.ofl_last_kernel_name.restype = ctypes.c_char_p
@@ -1327,6 +1332,67 @@ def matrix_fit(vecs: torch.Tensor, ref: str, mask: torch.Tensor, dof: int, metho
         _check(lib.ofl_matrix_fit_f64(_ptr(v), vbs, half, 1 if ref == 's' else 0, _ptr(m), mbs, n, h, w, int(dof),
                                       MATRIX_METHODS[method], _ptr(ws), _ptr(out), _ptr(info), _stream(dev)), "ofl_matrix_fit_f64")
     return out, info
+
+
+# -- Flow.error_stats / epe_map / epe (no counterpart in the reference): ofl_metrics.hip ------------------------------
+ERROR_RECORD = 16             # doubles per image: count, sum e, max e, 4 x over a threshold, Fl, 3 x speed count, 3 x speed sum e, 0, 0
+ERROR_MAX_THRESHOLDS = 4
+
+
+def _error_operands(est, gt, est_mask, gt_mask, dev, n):
+    e, ebs, ehalf = _vis_flow(est, dev, n)
+    g, gbs, ghalf = _vis_flow(gt, dev, n)
+    em, embs = (None, 0) if est_mask is None else _planes(est_mask, dev, torch.bool, n, "mask")
+    gm, gmbs = (None, 0) if gt_mask is None else _planes(gt_mask, dev, torch.bool, n, "ground-truth mask")
+    # (the tensors are returned to stay alive until the launch is queued)
+    return (e, g, em, gm), (_ptr(e), ebs, ehalf, _ptr(g), gbs, ghalf, _ptr(em), embs, _ptr(gm), gmbs)
+
+
+def flow_error(est: torch.Tensor, gt: torch.Tensor, est_mask: torch.Tensor = None, gt_mask: torch.Tensor = None, thresholds=(),
+               want_map: bool = False):
+    """The error records of an estimate against a ground truth (ofl_flow_error_f64): vectors [N,2,H,W] fp32 or fp16 as
+    stored, masks [N,H,W] bool or None (all True), up to four fp32 `thresholds`.  Returns (float64 [N,16] records, fp32 [N,H,W] map of
+    the end-point error or None), both on the HIP device; nothing is read back."""
+    lib, dev = load_library(), device(est, gt)
+    n, _, h, w = est.shape
+    thr = [float(t) for t in thresholds]
+    if len(thr) > ERROR_MAX_THRESHOLDS:
+        raise ValueError("oflibpytorch_amd: %d thresholds, at most %d" % (len(thr), ERROR_MAX_THRESHOLDS))
+    with _on(dev):
+        keep, args = _error_operands(est, gt, est_mask, gt_mask, dev, n)
+        nbytes = int(lib.ofl_flow_error_workspace_bytes(n, h, w))
+        _check(min(nbytes, 0), "ofl_flow_error_workspace_bytes")
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        rec = torch.empty((n, ERROR_RECORD), dtype=torch.float64, device=dev)
+        emap = torch.empty((n, h, w), dtype=torch.float32, device=dev) if want_map else None
+        _check(lib.ofl_flow_error_f64(*args, len(thr), *(thr + [0.0] * (ERROR_MAX_THRESHOLDS - len(thr))), _ptr(ws), _ptr(emap),
+                                      _ptr(rec), n, h, w, _stream(dev)), "ofl_flow_error_f64")
+    return rec, emap
+
+
+def flow_epe_grad(est: torch.Tensor, gt: torch.Tensor, est_mask: torch.Tensor, gt_mask: torch.Tensor, scale: torch.Tensor,
+                  want_est: bool = True, want_gt: bool = False):
+    """The backward of the per-image mean end-point error (ofl_flow_epe_grad_f32): `scale` fp32 [N] on the device (upstream gradient /
+    count).  Returns (grad_est, grad_gt): fp32 [N,2,H,W] on the HIP device, or None where not wanted."""
+    lib, dev = load_library(), device(est, gt)
+    n, _, h, w = est.shape
+    with _on(dev):
+        keep, args = _error_operands(est, gt, est_mask, gt_mask, dev, n)
+        sc = scale.detach().to(dev, torch.float32).contiguous()
+        g_est = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev) if want_est else None
+        g_gt = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev) if want_gt else None
+        _check(lib.ofl_flow_epe_grad_f32(*args, _ptr(sc), _ptr(g_est), _ptr(g_gt), n, h, w, _stream(dev)), "ofl_flow_epe_grad_f32")
+    return g_est, g_gt
+
+
+def flow_epe(est: torch.Tensor, gt: torch.Tensor, est_mask: torch.Tensor = None, gt_mask: torch.Tensor = None) -> torch.Tensor:
+    """The per-image mean end-point error, fp32 [N]: the float64 quotient of a record's sum and count rounded once (NaN at count 0).
+    When autograd is recording and either flow requires a gradient, the call goes through `_autograd.EpeFn`."""
+    if _wants_grad(est, gt):
+        from . import _autograd
+        return _autograd.EpeFn.apply(est, gt, est_mask, gt_mask)
+    rec, _ = flow_error(est, gt, est_mask, gt_mask, (), False)
+    return (rec[:, 1] / rec[:, 0]).to(torch.float32)
 
 
 # -- Flow.visualise_arrows (flow_class.py:1358-1496): ofl_arrows.hip ---------------------------------------------------------------

@@ -11,6 +11,7 @@ Differences from the reference that do not change results:
   * an all-True default mask is kept implicit (`None`) until somebody asks for `.mask`;
   * intermediates produced by the kernels are not re-validated eagerly.
 """
+import math
 import warnings
 import weakref
 from typing import Tuple, Union
@@ -1186,6 +1187,65 @@ class Flow(object):
         return mats.to(self._device)
 
     # ------------------------------------------------------------------------------------------
+    # scoring against a ground truth (an extension: the reference has no such methods)
+    # ------------------------------------------------------------------------------------------
+    def _error_operands(self, gt: FlowAlias, consider_mask: bool):
+        """The checks the three scoring methods share; returns (gt on this flow's device, this flow's mask, gt's mask) with None for
+        a mask that does not count."""
+        if not isinstance(gt, Flow):
+            raise TypeError("Error scoring flow: Gt needs to be of type 'Flow'")
+        if self.shape != gt.shape:
+            raise ValueError("Error scoring flow: Flow fields need to have the same shape, including batch size")
+        if self.ref != gt.ref:
+            raise ValueError("Error scoring flow: Flow fields need to have the same reference")
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError("Error scoring flow: Consider_mask needs to be boolean")
+        if self._device != gt._device:
+            gt = gt.to_device(self._device)
+        return gt, (self._mask if consider_mask else None), (gt._mask if consider_mask else None)
+
+    def error_stats(self, gt: FlowAlias, consider_mask: bool = None, thresholds: Union[list, tuple] = None) -> dict:
+        """Score this flow as an estimate of the ground truth `gt` (equal shape and reference), per batch element over the pixels
+        valid in both masks (every pixel if `consider_mask` is False).  Returns a dict of tensors on the flow's device:
+        'count' int64 [N]; 'epe' float64 [N], the mean end-point error (NaN where count is 0); 'max' float64 [N]; 'outliers' float64
+        [N,K], the share of pixels whose error is over (strictly) each of the K `thresholds` (1 to 4, default (1, 3, 5) px); 'fl'
+        float64 [N], KITTI's outlier rate (error over 3 px and over 5 % of the true speed); 'speed_count' int64 [N,3] and
+        'speed_epe' float64 [N,3], the pixels and their mean error by true speed in [0, 10), [10, 40), [40, inf) px.  One pass of
+        ofl_metrics.hip over both flows, float64 sums in a fixed order (bitwise reproducible, independent of the batch; DESIGN.md
+        3.16); nothing is read back to the host.  Not differentiable: see :meth:`epe`."""
+        gt, mask, gt_mask = self._error_operands(gt, consider_mask)
+        thresholds = (1, 3, 5) if thresholds is None else thresholds
+        if not isinstance(thresholds, (list, tuple)):
+            raise TypeError("Error scoring flow: Thresholds needs to be a list or a tuple")
+        if not 1 <= len(thresholds) <= _native.ERROR_MAX_THRESHOLDS:
+            raise ValueError("Error scoring flow: Thresholds list or tuple needs to have length 1 to 4")
+        if not all(isinstance(t, (int, float)) and not isinstance(t, bool) for t in thresholds):
+            raise TypeError("Error scoring flow: Thresholds needs to hold integers or floats")
+        if not all(math.isfinite(t) and t >= 0 for t in thresholds):
+            raise ValueError("Error scoring flow: Thresholds need to be finite and not negative")
+        k = len(thresholds)
+        rec, _ = _native.flow_error(self._fv, gt._fv, mask, gt_mask, tuple(thresholds), False)
+        rec = rec.to(self._device)
+        count = rec[:, 0]
+        return {'count': count.to(torch.int64), 'epe': rec[:, 1] / count, 'max': rec[:, 2].clone(),
+                'outliers': rec[:, 3:3 + k] / count[:, None], 'fl': rec[:, 7] / count,
+                'speed_count': rec[:, 8:11].to(torch.int64), 'speed_epe': rec[:, 11:14] / rec[:, 8:11]}
+
+    def epe_map(self, gt: FlowAlias, consider_mask: bool = None) -> torch.Tensor:
+        """The end-point error of every pixel against the ground truth `gt`: float32 N-H-W on the flow's device, 0 where a pixel is
+        not valid in both masks (every pixel counts if `consider_mask` is False).  Not differentiable: see :meth:`epe`."""
+        gt, mask, gt_mask = self._error_operands(gt, consider_mask)
+        return _native.flow_error(self._fv, gt._fv, mask, gt_mask, (), True)[1].to(self._device)
+
+    def epe(self, gt: FlowAlias, consider_mask: bool = None) -> torch.Tensor:
+        """The mean end-point error against the ground truth `gt` per batch element: float32 [N] on the flow's device (the float64
+        mean of :meth:`error_stats` rounded once; NaN for an element without a valid pixel).  Differentiable with respect to the
+        vectors of either flow -- the supervised loss of a flow network; an element without a valid pixel has gradient 0."""
+        gt, mask, gt_mask = self._error_operands(gt, consider_mask)
+        return _native.flow_epe(self._fv, gt._fv, mask, gt_mask).to(self._device)
+
+    # ------------------------------------------------------------------------------------------
     # composition (flow_class.py:1648-1810)
     # ------------------------------------------------------------------------------------------
     def combine_with(self, flow: FlowAlias, mode: int, thresholded: bool = None) -> FlowAlias:
@@ -1410,6 +1470,6 @@ def _combine_plan(mode: int, self_ref: str, other_ref: str, out_ref: str) -> _Co
 
 # the public methods that read a flow's flag word: each starts a new validation epoch under set_revalidate_every_call(True)
 for _name in ('apply', 'track', 'switch_ref', 'invert', 'valid_target', 'valid_source', 'get_padding', 'is_zero', 'combine_with',
-              'combine', 'visualise', 'visualise_arrows'):
+              'combine', 'visualise', 'visualise_arrows', 'error_stats', 'epe_map', 'epe'):
     setattr(Flow, _name, _public(getattr(Flow, _name)))
 del _name

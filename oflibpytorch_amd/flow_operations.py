@@ -78,6 +78,21 @@ def get_flow_matrix(flow, ref: str, dof: int = None, method: str = None) -> torc
     return m if len(flow.shape) > 3 else m.squeeze(0)
 
 
+def flow_error_stats(flow, gt, mask=None, gt_mask=None, thresholds: Union[list, tuple] = None) -> dict:
+    """Flow(flow, mask=mask).error_stats(Flow(gt, mask=gt_mask), thresholds=thresholds): the dict of Flow.error_stats for arrays /
+    tensors (N-)2-H-W or (N-)H-W-2 with optional masks (N-)H-W; 3-D in -> entries without the batch dimension.  An extension
+    (DESIGN.md 3.16): the reference has no such function."""
+    stats = Flow(flow, 't', mask).error_stats(Flow(gt, 't', gt_mask), thresholds=thresholds)
+    return stats if len(flow.shape) > 3 else {k: v.squeeze(0) for k, v in stats.items()}
+
+
+def flow_epe(flow, gt, mask=None, gt_mask=None) -> torch.Tensor:
+    """Flow(flow, mask=mask).epe(Flow(gt, mask=gt_mask)): the mean end-point error, float32 [N] (a scalar tensor for 3-D input),
+    differentiable with respect to tensor inputs.  An extension."""
+    e = Flow(flow, 't', mask).epe(Flow(gt, 't', gt_mask))
+    return e if len(flow.shape) > 3 else e.squeeze(0)
+
+
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
     """Concatenate flow objects of equal H, W, ref and device along the batch axis (flow_operations.py:458-483)"""
     if not isinstance(flows, (list, tuple)):
