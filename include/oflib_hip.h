@@ -223,17 +223,22 @@ int ofl_splat_finalize_f32(const float* accum,
  * processed in groups of 3), else it returns OFL_E_UNSUPPORTED and the caller
  * uses ofl_splat_fwd_f32 + ofl_splat_finalize_f32.
  *   workspace      int32[ofl_splat_tiled_workspace_ints(n, h, w)]: 8 statistics words | one flag per image | list
- *                  lengths | 256 list entries per destination tile
- *                  (fixed addresses; ~2 B/px).  Contents irrelevant on entry; afterwards workspace[0] = 1 if some
- *                  IMAGE took the two-pass path, workspace[1] = number of tiles that left the exact path,
+ *                  lengths | 256 list entries per destination tile | the redo list (up to 16 bands of 2 words per tile),
+ *                  sized for ONE pass of the batch (fixed addresses; ~2 B/px).  Contents irrelevant on entry: the first
+ *                  pass zeroes statistics, flags and lengths in-stream, a later pass the redo counters, flags and lengths
+ *                  (the statistics accumulate over the call), every further channel group the redo counters; list
+ *                  entries are read only below the length their pass wrote.  Afterwards workspace[0] = 1
+ *                  if some IMAGE took the two-pass path, workspace[1] = number of tiles that left the exact path,
  *                  workspace[2] = number of such images
  *   data_b         optional [*,C,H,W] fp32 (C <= 2, else OFL_E_ARG): the data splatted is data - data_b (ONE fp32 subtraction per value, the
  *                  reference's `flow - self` in combine_with modes 1-2, flow_class.py:1763,1768), then x data_sign
  *   dst_flags      optional int32[N] (C == 2 only, else OFL_E_ARG; zeroed in-stream): the flag word (see
  *                  ofl_flow_flags_f32) of the OUTPUT read as a flow under its `valid` mask -- a by-product that spares
  *                  the caller the validation pass (utils.py:98, flow_class.py:1226-1244) over an intermediate flow
- *   accum_fallback fp32[ofl_splat_tiled_pass_images(n, h, w) * (1 + C + with_mask_chan) * H * W]  (one pass of the batch)
- *                  used (and zeroed in-stream, per image) only for an image in which a destination tile is touched by
+ *   accum_fallback fp32[ofl_splat_tiled_fallback_images(n, planes, h, w) * planes * H * W] with planes = 1 + min(C, 3) +
+ *                  with_mask_chan (at most one pass of the batch, capped at 1 GiB: flagged images beyond that are served
+ *                  in rounds).  Contents irrelevant on entry:
+ *                  used (and zeroed in-stream, per image and round, by the kernel that then adds into it) only for an image in which a destination tile is touched by
  *                  more than 256 source subtiles (16 x 2 pixels each) or a subtile spreads over more than 256 destination tiles: the two-pass
  *                  global-atomics path then runs for THAT image inside the same call, decided on the device (no host
  *                  sync; tolerance instead of bit-exactness).  A heavy fold of the flow (> 64 source pixels ending in
@@ -552,7 +557,7 @@ int ofl_warp_bwd_grad_f32(const float* flow, int64_t flow_bs, float flow_sign,
  * grad_density optional [N,H,W] (upstream gradient of the density output).  grad_data [N,C,H,W], grad_xy [N,2,H,W]
  * (x then y; for a flow operand grad_flow = flow_sign * grad_xy) -- either may be NULL.  C <= 3 per call, else
  * OFL_E_UNSUPPORTED (split the channels; grad_density with the first group only; the grad_xy of the groups add up).
- * scratch: fp32[N * 4 * H * W] (a first pass leaves g_c / max(D, 1e-3) and the density term of every destination pixel in
+ * scratch: fp32[N * 4 * H * W], contents irrelevant on entry (a first pass leaves g_c / max(D, 1e-3) and the density term of every destination pixel in
  * one 16-byte slot: the divisions are done once, and the gather loads one slot per corner instead of 2 C + 1 scalars).
  */
 int ofl_splat_grad_f32(const float* flow, int64_t flow_bs, float flow_sign,
@@ -580,7 +585,8 @@ int ofl_sample_pts_grad_f32(const float* flow, int64_t flow_bs, const float* pts
  * Extents of the positions a flow reaches, under its mask -- the reduction of Flow.get_padding (flow_class.py:1196-1219):
  *   pos = -(sign * thr(v) - grid) per component (thr: threshold_vectors, |v| < 1e-3 -> 0); sign = +1 for 't', -1 for 's'
  *   extents[n] = { min y, max y, min x, max x, any valid pixel (0 / 1) }   fp32[N][5]
- * workspace int32[5 N] (scratch).  min / max are exact in any order.
+ * workspace int32[5 N] (scratch; contents irrelevant on entry: flow_extents_init_kernel writes all 5 N words first).  extents: written,
+ * every one of the 5 N floats (an image without a valid pixel: the decoded start values and 0).  min / max are exact in any order.
  */
 int ofl_flow_extents_f32(const float* flow, int64_t flow_bs, const uint8_t* mask, int64_t mask_bs, float sign,
                          int32_t* workspace, float* extents, int32_t n, int32_t h, int32_t w, void* stream);
@@ -692,7 +698,10 @@ int ofl_matrix_fit_f64(const void* flow, int64_t flow_bs, int32_t flow_half, int
  * (so h, w >= 2), else OFL_E_ARG; n <= 65535, n * P < 2^31.  Three calls on one stream, one workspace:
  *
  * ofl_arrows_workspace_ints(n, h, w, grid_dist): int32 words of the workspace (header | per-image sums | magnitudes | records | tile counts,
- *   offsets and cursors), or an OFL_E_* code.
+ *   offsets and cursors), or an OFL_E_* code.  Contents irrelevant on entry of each of the three calls below, as are those of `list`:
+ *   the magnitudes are written by ofl_arrows_scale_f32 before its select reads them; ofl_arrows_plan zeroes the tile counts in-stream
+ *   and writes every word of every record, every offset, every per-image sum and the header; ofl_arrows_u8 zeroes the cursors
+ *   in-stream and reads only the list entries it has just filled.
  *
  * ofl_arrows_scale_f32 <- `scaling is None` (flow_class.py:1456-1458): the magnitudes of the thresholded flow at the grid points
  *   (cartToPolar, FMA form), np.percentile(., 99) over all n * P of them (numpy 2.2.6 'linear' in fp32; exact order statistics
@@ -735,7 +744,9 @@ int ofl_arrows_u8(const uint8_t* img, int64_t img_bs, int32_t img_layout, const 
  * h, w >= 2, h * w < 2^30, nf <= 65535.  flow fp32 [nf,2,h,w] (flow_bs elements between images), mask uint8 [nf,h,w].
  *
  * ofl_mesh_workspace_ints(nf, h, w, points): int32 words of the workspace (header | tile offsets, counts, cursors), or an OFL_E_* code;
- *   points = 0: pixel queries over 64 x 16 tiles (ofl_mesh_apply), 1: point queries over 8 x 8 tiles (ofl_mesh_points).
+ *   points = 0: pixel queries over 64 x 16 tiles (ofl_mesh_apply), 1: point queries over 8 x 8 tiles (ofl_mesh_points).  Contents
+ *   irrelevant on entry, as are those of `list`: ofl_mesh_plan zeroes the counts in-stream and writes every offset and the header,
+ *   ofl_mesh_apply / ofl_mesh_points zero the cursors in-stream and read only the list entries they have just filled.
  *
  * ofl_mesh_plan: the number of quads whose box touches each tile and the exclusive scan of those counts.  Afterwards workspace[0..1]
  *   (int64) = the list entries of all tiles: the caller reads it back and sizes `list` from it.  Nothing is capped: a quad is listed in

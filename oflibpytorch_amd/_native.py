@@ -949,10 +949,13 @@ def warp_bwd_grad_x16(flow, src16, grad_out16, *, flow_sign=1.0, g_scale=1.0, wa
     [N,C,H,W] contiguous, of one 16-bit dtype -> (grad_src in src16.dtype | None, grad_flow fp32 [N,2,H,W] | None) -- bit-identical
     to `warp_bwd_grad` on the up-converted tensors followed by `.to(dtype)`.  None when the call is not of that kind (another dtype or
     device, a source broadcast over the batch: its gradient is summed over the batch in fp32) or the library declines a launch;
-    nothing has been computed then and the caller takes `warp_bwd_grad`."""
+    nothing has been computed then and the caller takes `warp_bwd_grad`.  A source gradient under |g_scale| != 1 is declined too: the
+    gather splat takes a sign only, and scaling the 16-bit gradient first would round where `warp_bwd_grad` (which scales in fp32) does not."""
     dt = src16.dtype
     if (dt not in _X16_DTYPES or grad_out16.dtype != dt or src16.device.type != 'cuda' or grad_out16.device != src16.device
             or src16.dim() != 4 or src16.shape != grad_out16.shape or not (want_src or want_flow)):
+        return None
+    if want_src and abs(float(g_scale)) != 1.0:
         return None
     n, c, h, w = grad_out16.shape
     if w < 4 or h < 2 or h * w >= (1 << 24) or h >= 32760 or w >= 32760 or flow.shape[0] not in (1, n):
@@ -1039,8 +1042,11 @@ def warp_bwd_grad_nhwc(flow, src, grad_out, *, flow_sign=1.0, g_scale=1.0, want_
     planar routes' gather splat between the library's two layout copies (ofl_nhwc_to_planes of the upstream gradient,
     ofl_planes_to_nhwc of the result; an N-H-W-C gather splat: DESIGN.md section 8) and never reads the source.  None when the call
     is not of this kind (a planar or strided gradient, another dtype, a source broadcast over the batch, a frame the gather splat does
-    not take) or the library declines a launch; nothing observable has happened then and the caller takes the planar route."""
+    not take, a source gradient under |g_scale| != 1: the gather splat takes a sign only) or the library declines a launch; nothing
+    observable has happened then and the caller takes the planar route."""
     if not (want_src or want_flow) or src.device.type != 'cuda':
+        return None
+    if want_src and abs(float(g_scale)) != 1.0:
         return None
     kind = _nhwc_grad_kind(src, grad_out)
     n, c, h, w = grad_out.shape if grad_out.dim() == 4 else (0, 0, 0, 0)

@@ -236,6 +236,24 @@ def test_declined_calls_take_the_present_route(dtype, dev):
     assert torch.equal(res[0][1], res[1][1])
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=str)
+def test_a_scaled_source_gradient_is_declined_before_anything_runs(dtype, dev):
+    """`warp_bwd_grad_x16` used to hand g_scale to ofl_splat_sum_x16 as its data sign, which takes +-1 only: |g_scale| != 1 with
+    want_src raised (status -3) after the flow gradient had been computed.  It is declined up front now, the caller's
+    `warp_bwd_grad` scales in fp32; +-1 and the flow gradient alone are still native."""
+    from oflibpytorch_amd import _native
+    n, c, h, w = 2, 3, 37, 53
+    vecs, t, g = _flow(n, h, w, dev), _target(n, c, h, w, dtype, dev, seed=4), _upstream((n, c, h, w), dtype, dev, seed=5)
+    assert _native.warp_bwd_grad_x16(vecs, t, g, g_scale=0.5) is None
+    assert _native.warp_bwd_grad_x16(vecs, t, g, g_scale=-2.0, want_flow=False) is None
+    gs, gf = _native.warp_bwd_grad_x16(vecs, t, g, g_scale=0.5, want_src=False)
+    assert gs is None and torch.equal(gf, _native.warp_bwd_grad(vecs, t.float(), g.float(), g_scale=0.5, want_src=False)[1])
+    gs, gf = _native.warp_bwd_grad_x16(vecs, t, g, g_scale=-1.0)
+    rs, rf = _native.warp_bwd_grad(vecs, t.float(), g.float(), g_scale=-1.0)
+    _same_bits(gs, rs.to(dtype), "gradient wrt the target")
+    assert torch.equal(gf, rf)
+
+
 # ---- (7) both families of the flow-gradient launcher -------------------------------------------------------------------
 # thresholds in the kernels' 32-wide geometry: g1 = 32 x 16 tiles, g4 = 32 x 64 groups of the launch.  W % 4 == 0: row tables with one
 # tile per block below g1 = 5000, four from g4 = 5800, two between; other widths: the four-tile column kernel on the sheared rectangle.

@@ -164,6 +164,24 @@ def test_the_flow_gradient_equals_the_planar_routes_bit_for_bit(c, dtype, dev):
         _same_bits(got, ref, (c, h, w, "non-finite gradient"))
 
 
+@pytest.mark.parametrize("dtype", DTYPES, ids=str)
+def test_a_scaled_source_gradient_is_declined_before_anything_runs(dtype, dev):
+    """`warp_bwd_grad_nhwc` used to hand g_scale to the gather splat as its data sign, which takes +-1 only: |g_scale| != 1 with
+    want_src raised (status -3) after the first layout copy.  It is declined up front now (the planar route scales in fp32); +-1
+    and the flow gradient alone are still native."""
+    from oflibpytorch_amd import _native
+    n, c, h, w = 2, 4, 37, 53
+    vecs, s, g = _flow(n, h, w, dev), _target(n, c, h, w, dtype, dev, seed=1), _target(n, c, h, w, dtype, dev, seed=2)
+    assert _native.warp_bwd_grad_nhwc(vecs, s, g, g_scale=0.5) is None
+    assert _native.warp_bwd_grad_nhwc(vecs, s, g, g_scale=-2.0, want_flow=False) is None
+    got = _native_flow_grad(vecs, s, g, flow_sign=1.0, g_scale=0.5)
+    assert torch.equal(got.view(torch.int32), _planar_flow_grad(vecs, s, g, flow_sign=1.0, g_scale=0.5).view(torch.int32))
+    gs, gf = _native.warp_bwd_grad_nhwc(vecs, s, g, g_scale=-1.0)
+    rs, rf = _native.warp_bwd_grad(vecs, s.float().contiguous(), g.float().contiguous(), g_scale=-1.0)
+    assert gs.is_contiguous(memory_format=CL) and gs.dtype == dtype
+    assert torch.equal(gs.contiguous().view(BITS[dtype]), rs.to(dtype).view(BITS[dtype])) and torch.equal(gf, rf)
+
+
 # ---- (3) the whole backward through the public API ---------------------------------------------------------------------
 def _backward_both(call, vecs, t, g, *, flow_grad=True, target_grad=True):
     """`call(v, t)` on the channels_last target with the channels_last gradient against the same call on contiguous copies; returns
