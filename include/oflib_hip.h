@@ -846,6 +846,49 @@ int ofl_flow_epe_grad_f32(const void* est, int64_t est_bs, int32_t est_half, con
                           const uint8_t* est_mask, int64_t est_mask_bs, const uint8_t* gt_mask, int64_t gt_mask_bs, const float* scale,
                           float* grad_est, float* grad_gt, int32_t n, int32_t h, int32_t w, void* stream);
 
+/*
+ * The forward-backward consistency check of two flows (ofl_consistency.hip): Flow.consistency / consistency_mask /
+ * filter_consistent.  An extension: the reference has no such function.  `a` is a flow from frame 1 to frame 2, `back` a flow from frame 2
+ * to frame 1, both of one reference: flow_sign -1 for 's' flows (the partner of pixel p is `back` at p + a(p)), +1 for 't' flows (at
+ * x - a(x)).  Per pixel, every step fp32 with one rounding per operation (the fused multiply-adds are those of the backward warp):
+ *   (bu, bv), mr   the two planes of `back` and the validity of its taps sampled bilinearly at unnormalise(grid - flow_sign a), in the
+ *                  expressions of ofl_warp_bwd_f32: a tap outside the frame contributes 0, a tap where back_mask is 0 contributes 0 to mr
+ *   known          (mr > 0.99999f) and a_mask (a NULL mask is all True); a non-finite vector of `a` fails the comparisons: not known
+ *   e              sqrt(du du + dv dv) with du = u + bu, dv = v + bv, the root correctly rounded
+ *   consistent     known and du du + dv dv <= alpha ((u u + v v) + (bu bu + bv bv)) + beta        (inclusive)
+ * du, dv and known carry the bits of the vectors and the mask that mode 3 of combine_with gives (ofl_warp_bwd_f32 with the addend).
+ *
+ * ofl_flow_consistency_workspace_bytes(n, h, w): bytes of the workspace of ofl_flow_consistency_f32, or OFL_E_ARG for sizes that call
+ *   rejects.
+ *
+ * ofl_flow_consistency_f32:
+ *   a, back            [*,2,H,W] fp32 (half = 0) or fp16 (1: up-converted in registers, exact), a_bs / back_bs elements between images
+ *                      (0 broadcasts one image); aligned to their element.  Never written.
+ *   a_mask, back_mask  optional [*,H,W] bytes (any non-zero byte is True), batch strides in bytes.  Never written.
+ *   flow_sign          +-1 (above); alpha, beta: finite and >= 0
+ *   workspace          device memory of ofl_flow_consistency_workspace_bytes(n, h, w) bytes, 8-byte aligned; needed (and touched) only
+ *                      when `record` is given.  Its contents are irrelevant on entry: every word the second launch reads is written by
+ *                      the first.
+ *   error              optional fp32 [n,h,w]: e, 0 where the pixel is not known
+ *   consistent, known  optional uint8 [n,h,w]: bytes 0 / 1
+ *   record             optional float64 [n, OFL_CONSISTENCY_RECORD], 8-byte aligned, per image: [0] known pixels  [1] consistent pixels
+ *                      [2] sum e over the known pixels  [3] max e over the known pixels (0 without one)  [4] sum e over the consistent
+ *                      pixels  [5 .. 7] 0.  Counts are exact; sums are float64 sums of the fp32 e in the fixed order of
+ *                      ofl_flow_error_f64 (lane, butterfly, waves, blocks ascending; the number of blocks depends on h * w only): no
+ *                      float atomics, an image's record has the same bits in any batch and on any run.
+ *   Every element of every output given is WRITTEN (not accumulated into; nothing to clear beforehand); an output that is NULL is not
+ *   written; at least one must be given.  OFL_E_ARG, before any launch, for: n outside 1 .. 65535, h or w < 2, h * w >= 2^31, a flow_sign
+ *   other than +-1, alpha or beta negative or not finite, a NULL flow pointer, all four outputs NULL, a record without a workspace, a
+ *   negative stride, a misaligned pointer.  One launch, two with a record: ofl_last_kernel_name() then names
+ *   flow_consistency_finish_kernel.
+ */
+#define OFL_CONSISTENCY_RECORD 8
+int64_t ofl_flow_consistency_workspace_bytes(int32_t n, int32_t h, int32_t w);
+int ofl_flow_consistency_f32(const void* a, int64_t a_bs, int32_t a_half, const void* back, int64_t back_bs, int32_t back_half,
+                             const uint8_t* a_mask, int64_t a_mask_bs, const uint8_t* back_mask, int64_t back_mask_bs, float flow_sign,
+                             float alpha, float beta, void* workspace, float* error, uint8_t* consistent, uint8_t* known, double* record,
+                             int32_t n, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_warp_bwd_x16", "ofl_warp_bwd_grad_x16", "ofl_splat_sum_x16", "ofl_warp_bwd_nhwc",
             "ofl_warp_bwd_grad_nhwc", "ofl_nhwc_to_planes", "ofl_planes_to_nhwc",
             "ofl_png_unfilter", "ofl_png_grey8", "ofl_decode_kitti", "ofl_decode_flo",
-            "ofl_flow_error_workspace_bytes", "ofl_flow_error_f64", "ofl_flow_epe_grad_f32")
+            "ofl_flow_error_workspace_bytes", "ofl_flow_error_f64", "ofl_flow_epe_grad_f32",
+            "ofl_flow_consistency_workspace_bytes", "ofl_flow_consistency_f32")     # (the last two: declared and bound by _consistency.py)
 _lib = None
 _load_lock = threading.RLock()
 

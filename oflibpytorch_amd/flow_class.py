@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _native, distributed
+from . import _consistency, _native, distributed
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
@@ -1246,6 +1246,73 @@ class Flow(object):
         return _native.flow_epe(self._fv, gt._fv, mask, gt_mask).to(self._device)
 
     # ------------------------------------------------------------------------------------------
+    # forward-backward consistency (an extension: the reference has no such methods)
+    # ------------------------------------------------------------------------------------------
+    def _consistency_operands(self, back: FlowAlias, alpha, beta, consider_mask: bool):
+        """The checks the three consistency methods share; returns the arguments of `_consistency.flow_consistency` up to beta."""
+        err = "Error checking flow consistency: "
+        if not isinstance(back, Flow):
+            raise TypeError(err + "Back needs to be of type 'Flow'")
+        if self.shape != back.shape:
+            raise ValueError(err + "Flow fields need to have the same shape, including batch size")
+        if self.ref != back.ref:
+            raise ValueError(err + "Flow fields need to have the same reference: switch_ref one of them")
+        if self.shape[1] < 2 or self.shape[2] < 2:
+            raise ValueError(err + "Flow fields need to be at least 2 pixels high and wide")
+        alpha = 0.01 if alpha is None else alpha
+        beta = 0.5 if beta is None else beta
+        for name, value in (("Alpha", alpha), ("Beta", beta)):
+            if not isinstance(value, (int, float)) or isinstance(value, bool):
+                raise TypeError(err + name + " needs to be an integer or a float")
+            if not (math.isfinite(value) and value >= 0):
+                raise ValueError(err + name + " needs to be finite and not negative")
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError(err + "Consider_mask needs to be boolean")
+        if self._device != back._device:
+            back = back.to_device(self._device)
+        return (self._fv, back._fv, self._mask if consider_mask else None, back._mask if consider_mask else None,
+                -1.0 if self._ref == 's' else 1.0, float(alpha), float(beta))
+
+    def consistency(self, back: FlowAlias, alpha: float = None, beta: float = None, consider_mask: bool = None) -> dict:
+        """The forward-backward check of this flow (frame 1 to frame 2) against `back`, a flow from frame 2 to frame 1 of equal shape
+        and reference.  The partner of a pixel is `back` sampled bilinearly where this flow points -- at p + self(p) for 's' flows, at
+        x - self(x) for 't' flows, the arithmetic of :meth:`combine_with` mode 3.  A pixel is KNOWN where the partner's taps lie in
+        the frame and are valid in `back.mask` and the pixel is valid in this flow's mask (with `consider_mask` False: the frame test
+        alone); its error e is the length of the round trip self + partner; it is CONSISTENT where it is known and
+        e^2 <= alpha (|self|^2 + |partner|^2) + beta (inclusive; defaults 0.01 and 0.5 as in UnFlow).  Returns a dict of tensors on
+        the flow's device: 'error' float32 [N,H,W] (0 where not known), 'consistent' and 'known' bool [N,H,W], 'count' and
+        'consistent_count' int64 [N], 'rate' float64 [N] (consistent / known, NaN without a known pixel), 'mean_error' (over the
+        known pixels), 'max_error' and 'mean_error_consistent' float64 [N].  One pass of ofl_consistency.hip: the composed flow is
+        never written, float64 sums in a fixed order (bitwise reproducible, independent of the batch), nothing is
+        read back to the host.  Not differentiable: the call runs on the detached vectors."""
+        err, cons, known, rec = _consistency.flow_consistency(*self._consistency_operands(back, alpha, beta, consider_mask))
+        err, cons, known, rec = (t.to(self._device) for t in (err, cons, known, rec))
+        count, ccount = rec[:, 0], rec[:, 1]
+        return {'error': err, 'consistent': cons, 'known': known, 'count': count.to(torch.int64),
+                'consistent_count': ccount.to(torch.int64), 'rate': ccount / count, 'mean_error': rec[:, 2] / count,
+                'max_error': rec[:, 3].clone(), 'mean_error_consistent': rec[:, 4] / ccount}
+
+    def consistency_mask(self, back: FlowAlias, alpha: float = None, beta: float = None, consider_mask: bool = None) -> torch.Tensor:
+        """The 'consistent' map of :meth:`consistency` alone: bool N-H-W on the flow's device (the kernel writes nothing else).  Not
+        differentiable."""
+        ops = self._consistency_operands(back, alpha, beta, consider_mask)
+        return _consistency.flow_consistency(*ops, want_error=False, want_known=False, want_record=False)[1].to(self._device)
+
+    def filter_consistent(self, back: FlowAlias, alpha: float = None, beta: float = None, consider_mask: bool = None) -> FlowAlias:
+        """This flow with its mask narrowed to the pixels :meth:`consistency_mask` finds consistent with `back`: same vectors (the
+        same tensor, not a copy) and reference, mask = self.mask & consistent.  Not differentiable with respect to `back`."""
+        mask = self._and_masks(self.consistency_mask(back, alpha, beta, consider_mask))
+        out = Flow._wrap(self._fv, self._ref, mask, self._device)
+        if self._flags_known():
+            # the vectors are this flow's: finiteness and the unmasked zero tests carry over; the masked ones can only lose bits under a
+            # narrower mask, so a word that has none of them set stays exact
+            word = self._flag_cache[1]
+            if not any(f & (_native.FLAG_NZ_MASKED | _native.FLAG_NZ_THR_MASKED) for f in word):
+                out._flag_cache = (out._key(), word)
+        return out
+
+    # ------------------------------------------------------------------------------------------
     # composition (flow_class.py:1648-1810)
     # ------------------------------------------------------------------------------------------
     def combine_with(self, flow: FlowAlias, mode: int, thresholded: bool = None) -> FlowAlias:
@@ -1470,6 +1537,7 @@ def _combine_plan(mode: int, self_ref: str, other_ref: str, out_ref: str) -> _Co
 
 # the public methods that read a flow's flag word: each starts a new validation epoch under set_revalidate_every_call(True)
 for _name in ('apply', 'track', 'switch_ref', 'invert', 'valid_target', 'valid_source', 'get_padding', 'is_zero', 'combine_with',
-              'combine', 'visualise', 'visualise_arrows', 'error_stats', 'epe_map', 'epe'):
+              'combine', 'visualise', 'visualise_arrows', 'error_stats', 'epe_map', 'epe', 'consistency', 'consistency_mask',
+              'filter_consistent'):
     setattr(Flow, _name, _public(getattr(Flow, _name)))
 del _name

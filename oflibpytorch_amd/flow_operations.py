@@ -93,6 +93,14 @@ def flow_epe(flow, gt, mask=None, gt_mask=None) -> torch.Tensor:
     return e if len(flow.shape) > 3 else e.squeeze(0)
 
 
+def flow_consistency(flow, back, ref: str, mask=None, back_mask=None, alpha: float = None, beta: float = None) -> dict:
+    """Flow(flow, ref, mask).consistency(Flow(back, ref, back_mask), alpha, beta): the dict of Flow.consistency for arrays / tensors
+    (N-)2-H-W or (N-)H-W-2 with optional masks (N-)H-W; 3-D in -> entries without the batch dimension.  An extension:
+    the reference has no such function."""
+    res = Flow(flow, ref, mask).consistency(Flow(back, ref, back_mask), alpha=alpha, beta=beta)
+    return res if len(flow.shape) > 3 else {k: v.squeeze(0) for k, v in res.items()}
+
+
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
     """Concatenate flow objects of equal H, W, ref and device along the batch axis (flow_operations.py:458-483)"""
     if not isinstance(flows, (list, tuple)):
