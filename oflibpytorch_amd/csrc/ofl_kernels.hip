@@ -1950,7 +1950,7 @@ __device__ __forceinline__ void splat_fwd_tiles(const SplatParams& p) {
             yv = p.ys[n * p.xy_bs + pix];
         }
         const bool wm = wmk ? (inside && wmk[fpix] != 0) : true;
-        if (!wm || zero) continue;  // weight * 0: contributes exactly nothing (utils.py:1123)
+        if (!wm || zero) continue;  // weight * 0 (utils.py:1123): an excluded pixel contributes nothing, whatever it holds
 
         const float x0 = floorf(xv), y0 = floorf(yv);
         const float x1 = x0 + 1.0f, y1 = y0 + 1.0f;
@@ -1963,6 +1963,8 @@ __device__ __forceinline__ void splat_fwd_tiles(const SplatParams& p) {
         wy[1] = (yv - y0) * (y1 == y1s ? 1.0f : 0.0f);
         const int ixs[2] = {(int)x0s, (int)x1s};
         const int iys[2] = {(int)y0s, (int)y1s};
+        const bool inx[2] = {x0 == x0s, x1 == x1s};   // the corner lies inside the frame
+        const bool iny[2] = {y0 == y0s, y1 == y1s};
 
         float mval = 0.0f;
         if (p.with_mask_chan) mval = ((cma ? cma[pix] != 0 : true) && (p.fw != 0 ? inside : true) && (cmb ? cmb[fpix] != 0 : true)) ? 1.0f : 0.0f;
@@ -1972,7 +1974,9 @@ __device__ __forceinline__ void splat_fwd_tiles(const SplatParams& p) {
 #pragma unroll
             for (int kx = 0; kx < 2; ++kx) {
                 const float wgt = wy[ky] * wx[kx];  // utils.py:1114
-                if (wgt == 0.0f) continue;          // adding +-0 never changes an accumulator that starts at +0
+                // DESIGN.md 3.2, the corner rule: every corner inside the frame receives wgt * data, a weight of 0 included
+                // (0 * NaN is NaN, as in the reference and in the gather kernel); a corner outside the frame nothing
+                if (!(iny[ky] && inx[kx])) continue;
                 const int64_t pos = (int64_t)iys[ky] * w + ixs[kx];  // utils.py:1118 (exact for h*w < 2^24)
                 atomicAdd(&acc[pos], wgt);
 #pragma unroll
@@ -2492,13 +2496,17 @@ __global__ __launch_bounds__(256) void splat_bin_kernel(const GatherParams p) {
 
 // weights and destination-local corner positions of one end point, exactly as the reference (utils.py:1098-1114)
 __device__ __forceinline__ void sp_corners(float xv, float yv, float wmax, float hmax, int dx0, int dy0,
-                                           float (&wx)[2], float (&wy)[2], int (&ix)[2], int (&iy)[2]) {
+                                           float (&wx)[2], float (&wy)[2], int (&ix)[2], int (&iy)[2], bool (&inx)[2], bool (&iny)[2]) {
     const float x0 = floorf(xv), y0 = floorf(yv), x1 = x0 + 1.0f, y1 = y0 + 1.0f;
     const float x0s = fminf(fmaxf(x0, 0.0f), wmax), x1s = fminf(fmaxf(x1, 0.0f), wmax);
     const float y0s = fminf(fmaxf(y0, 0.0f), hmax), y1s = fminf(fmaxf(y1, 0.0f), hmax);
     wx[0] = (x1 - xv) * (x0 == x0s ? 1.0f : 0.0f); wx[1] = (xv - x0) * (x1 == x1s ? 1.0f : 0.0f);
     wy[0] = (y1 - yv) * (y0 == y0s ? 1.0f : 0.0f); wy[1] = (yv - y0) * (y1 == y1s ? 1.0f : 0.0f);
     ix[0] = (int)x0s - dx0; ix[1] = (int)x1s - dx0; iy[0] = (int)y0s - dy0; iy[1] = (int)y1s - dy0;
+    inx[0] = x0 == x0s;      // the corner lies inside the frame
+    inx[1] = x1 == x1s;
+    iny[0] = y0 == y0s;
+    iny[1] = y1 == y1s;
 }
 
 // exchange with the neighbouring lane (lanes 2j <-> 2j + 1): the pair's partner owns the other half of a 4-pixel group
@@ -2802,8 +2810,8 @@ __device__ __forceinline__ void sp_tile_atomics(const GP& p, const SP& s, float*
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (!((q.on >> k) & 1u)) continue;
-            float wx[2], wy[2]; int ix[2], iy[2];
-            sp_corners(q.x[k], q.y[k], wmax, hmax, t.dx0, t.dy0, wx, wy, ix, iy);
+            float wx[2], wy[2]; int ix[2], iy[2]; bool inx[2], iny[2];
+            sp_corners(q.x[k], q.y[k], wmax, hmax, t.dx0, t.dy0, wx, wy, ix, iy, inx, iny);
             const bool invalid = MCH ? (((mc4 >> (8 * k)) & 1u) == 0u) : false;
 #pragma unroll
             for (int ky = 0; ky < 2; ++ky) {
@@ -2811,7 +2819,9 @@ __device__ __forceinline__ void sp_tile_atomics(const GP& p, const SP& s, float*
                 for (int kx = 0; kx < 2; ++kx) {
                     const float wgt = wy[ky] * wx[kx];
                     const int xl = ix[kx], yl = iy[ky];
-                    if (wgt == 0.0f || (uint32_t)xl >= (uint32_t)kSpTW || (uint32_t)(yl - r0) >= (uint32_t)(r1 - r0)) continue;
+                    // the corner rule of DESIGN.md 3.2: a corner inside the frame receives wgt * data, a weight of 0 included;
+                    // one outside the frame nothing
+                    if (!(inx[kx] && iny[ky]) || (uint32_t)xl >= (uint32_t)kSpTW || (uint32_t)(yl - r0) >= (uint32_t)(r1 - r0)) continue;
                     const int d = yl * kSpTW + xl;
                     atomicAdd(&acc[d], wgt);
 #pragma unroll

@@ -19,13 +19,13 @@ its float outputs are held to the bar of its existing test against that test's r
 non-finite value where the reference has none, and everything else it returns (masks, flag words, outputs no atomic writes) is still
 compared byte for byte.  The cases, by id prefix, with the kernel and the line of the atomic:
 
-  splat.fold                      LDS float atomics of a fold band   sp_tile_atomics            ofl_kernels.hip:2816
-  splat.list_limit                LDS float atomics of a fold band   sp_tile_atomics            ofl_kernels.hip:2816
-  splat.queue_capacity            global two-pass path (per image)   splat_fwd_tiles            ofl_kernels.hip:1977
-  splat.fallback_slots            global two-pass path (per image)   splat_fwd_tiles            ofl_kernels.hip:1977
-  splat.passes_rough              global two-pass path (per image)   splat_fwd_tiles            ofl_kernels.hip:1977
-  splat.narrow                    global two-pass path (W < 4)       splat_fwd_tiles            ofl_kernels.hip:1977
-  splat.two_pass                  global two-pass path (forced)      splat_fwd_tiles            ofl_kernels.hip:1977
+  splat.fold                      LDS float atomics of a fold band   sp_tile_atomics            ofl_kernels.hip:2826
+  splat.list_limit                LDS float atomics of a fold band   sp_tile_atomics            ofl_kernels.hip:2826
+  splat.queue_capacity            global two-pass path (per image)   splat_fwd_tiles            ofl_kernels.hip:1981
+  splat.fallback_slots            global two-pass path (per image)   splat_fwd_tiles            ofl_kernels.hip:1981
+  splat.passes_rough              global two-pass path (per image)   splat_fwd_tiles            ofl_kernels.hip:1981
+  splat.narrow                    global two-pass path (W < 4)       splat_fwd_tiles            ofl_kernels.hip:1981
+  splat.two_pass                  global two-pass path (forced)      splat_fwd_tiles            ofl_kernels.hip:1981
   grad.warp-2x9x3                 grad_src of ofl_warp_bwd_grad_f32  warp_grad_kernel           ofl_aux_kernels.hip:99
   grad.pts                        grad_flow of ofl_sample_pts_grad   sample_pts_kernel<true>    ofl_aux_kernels.hip:315
 
@@ -49,13 +49,13 @@ pytestmark = pytest.mark.gpu
 
 CL = torch.channels_last
 ATOMIC_EXCEPTIONS = {
-    "splat.fold": ("sp_tile_atomics", "ofl_kernels.hip:2816"),
-    "splat.list_limit": ("sp_tile_atomics", "ofl_kernels.hip:2816"),
-    "splat.queue_capacity": ("splat_fwd_tiles", "ofl_kernels.hip:1977"),
-    "splat.fallback_slots": ("splat_fwd_tiles", "ofl_kernels.hip:1977"),
-    "splat.passes_rough": ("splat_fwd_tiles", "ofl_kernels.hip:1977"),
-    "splat.narrow": ("splat_fwd_tiles", "ofl_kernels.hip:1977"),
-    "splat.two_pass": ("splat_fwd_tiles", "ofl_kernels.hip:1977"),
+    "splat.fold": ("sp_tile_atomics", "ofl_kernels.hip:2826"),
+    "splat.list_limit": ("sp_tile_atomics", "ofl_kernels.hip:2826"),
+    "splat.queue_capacity": ("splat_fwd_tiles", "ofl_kernels.hip:1981"),
+    "splat.fallback_slots": ("splat_fwd_tiles", "ofl_kernels.hip:1981"),
+    "splat.passes_rough": ("splat_fwd_tiles", "ofl_kernels.hip:1981"),
+    "splat.narrow": ("splat_fwd_tiles", "ofl_kernels.hip:1981"),
+    "splat.two_pass": ("splat_fwd_tiles", "ofl_kernels.hip:1981"),
     "grad.warp-2x9x3": ("warp_grad_kernel", "ofl_aux_kernels.hip:99"),
     "grad.pts": ("sample_pts_kernel<true>", "ofl_aux_kernels.hip:315"),
 }
