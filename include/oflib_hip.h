@@ -889,6 +889,55 @@ int ofl_flow_consistency_f32(const void* a, int64_t a_bs, int32_t a_half, const 
                              float alpha, float beta, void* workspace, float* error, uint8_t* consistent, uint8_t* known, double* record,
                              int32_t n, int32_t h, int32_t w, void* stream);
 
+/*
+ * The edge-aware smoothness penalty of a flow (which defines the numbers; ofl_smoothness.hip): Flow.smoothness /
+ * smoothness_map / smoothness_stats.  An extension: the reference has no such function.  Per pixel p = (i, j), every step fp32 with one
+ * rounding per operation; direction x is written out, direction y is the same along rows.
+ *   order 1   the term exists iff j + 1 < w:  d = f(i,j+1) - f(i,j) per component,  g = (sum_c |I_c(i,j+1) - I_c(i,j)|) / float(C)
+ *   order 2   the term exists iff 1 <= j and j + 1 < w:  d = (f(i,j-1) - (f(i,j) + f(i,j))) + f(i,j+1),
+ *             g = ((sum_c |I_c(i,j+1) - I_c(i,j-1)|) / float(C)) * 0.5f          (channels added in ascending order)
+ *   r = sqrt(du du + eps eps) + sqrt(dv dv + eps eps), both roots correctly rounded;  w = 1.0f without an image, else
+ *   w = float(exp(double(-(alpha g)))): the float64 exp of the fp32 argument, rounded once;  t_x(p) = w r.
+ * A term is valid iff it exists and every pixel it reads (2 / 3) is True in the mask (a NULL mask is all True); an invalid term is +0.0f.
+ * flow [*,2,H,W] fp32 (half = 0) or fp16 (1: up-converted in registers, exact), flow_bs elements between images (0 broadcasts one
+ * image); mask optional [*,H,W] bytes (any non-zero byte is True), mask_bs bytes between images; img optional [*,C,H,W], 1 <= C <= 4,
+ * fp32 (img_u8 = 0) or uint8 (1: a sample s is float(s) / 255.0f), img_bs elements between images (0 broadcasts one image).  Without
+ * an image, img_bs, img_channels and img_u8 are ignored and no image pointer is touched.  Inputs are never written.
+ *
+ * ofl_flow_smoothness_workspace_bytes(n, h, w): bytes of the workspace of ofl_flow_smoothness_f64 (8-byte aligned; every word the second
+ *   launch reads is written by the first: nothing to clear), or OFL_E_ARG for sizes that call rejects.
+ *
+ * ofl_flow_smoothness_f64: records float64 [n, OFL_SMOOTHNESS_RECORD], per image over its valid terms
+ *     [0] count_x   [1] count_y   [2] sum t_x   [3] sum t_y   [4] max over all valid terms (0 without one)   [5 .. 7] 0.
+ *   Counts are exact (integers up to the record).  Sums are float64 sums of the fp32 terms in a fixed order -- a lane's pixels
+ *   ascending, the lanes of a wave by a butterfly, the waves and then the blocks of an image in index order -- and the number of blocks
+ *   depends on (h, w) only: no float atomics, an image's record has the same bits in any batch and on any run.  smoothness_map
+ *   (optional) fp32 [n,h,w]: t_x(p) + t_y(p), one fp32 addition; the term is attributed to the left / upper pixel (order 1) or to the
+ *   centre pixel (order 2).  Every element of every output is WRITTEN.  Two launches: ofl_last_kernel_name() then names
+ *   flow_smoothness_finish_kernel.
+ *
+ * ofl_flow_smoothness_grad_f32: the backward of the per-image mean (sum_x + sum_y) / (count_x + count_y) with respect to the flow.  scale
+ *   fp32 [n] DEVICE memory (the upstream gradient / total count); grad fp32 [n,2,h,w], every element written.  For a valid term T and
+ *   each component, in float64: q_T = (double(w) double(d)) / sqrt(double(d) double(d) + double(eps) double(eps)), 0 where the root is
+ *   0.  grad(s) = float(double(scale) * sum_k coef_k q_Tk) over the valid terms that read s -- order 1: +1 from the term at s - 1, -1 from
+ *   the term at s; order 2: +1, -2, +1 from the terms at s - 1, s, s + 1 -- added x before y and lower term index first in float64,
+ *   rounded once; exactly 0 where no valid term reads s (so an image without a valid term, whose scale is not finite, has gradient 0).
+ *   The kernel gathers: every output pixel recomputes its 4 / 6 terms from the inputs; no scatter, no atomics.  The image carries no
+ *   gradient.
+ *
+ * OFL_E_ARG, before any launch, for: n outside 1 .. 65535, h or w < 1, h * w >= 2^31, an order other than 1 or 2, C outside 1 .. 4 (with
+ * an image), alpha or eps negative or not finite, a NULL flow, workspace, records, scale or grad pointer, a negative stride, a flag that
+ * is neither 0 nor 1, a pointer not aligned to its element (workspace, records: 8 bytes).
+ */
+#define OFL_SMOOTHNESS_RECORD 8
+int64_t ofl_flow_smoothness_workspace_bytes(int32_t n, int32_t h, int32_t w);
+int ofl_flow_smoothness_f64(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, const void* img,
+                            int64_t img_bs, int32_t img_channels, int32_t img_u8, int32_t order, float alpha, float eps, void* workspace,
+                            float* smoothness_map, double* records, int32_t n, int32_t h, int32_t w, void* stream);
+int ofl_flow_smoothness_grad_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
+                                 const void* img, int64_t img_bs, int32_t img_channels, int32_t img_u8, int32_t order, float alpha,
+                                 float eps, const float* scale, float* grad, int32_t n, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ implemented (`once_differentiable` raises).
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _native
+from . import _native, _smoothness
 
 
 def _reduce_to(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
@@ -231,3 +231,26 @@ class EpeFn(torch.autograd.Function):
         g_est, g_gt = _native.flow_epe_grad(est.detach(), gt.detach(), ctx.masks[0], ctx.masks[1], scale, want_est=bool(need_est),
                                             want_gt=bool(need_gt))
         return (_reduce_to(g_est, est) if need_est else None), (_reduce_to(g_gt, gt) if need_gt else None), None, None
+
+
+class SmoothnessFn(torch.autograd.Function):
+    """smoothness[n] = mean over the valid terms of the edge-aware smoothness penalty   (Flow.smoothness): fp32, rounded
+    once from the float64 quotient of the kernel's sums and counts; NaN for an image without a valid term, whose gradient is 0.
+    Differentiable with respect to the vectors only: the image is guidance.  An fp16-stored flow is saved as it is stored."""
+
+    @staticmethod
+    def forward(ctx, vecs, mask, img, order, alpha, eps):
+        img = None if img is None else img.detach()
+        rec, _ = _smoothness.flow_smoothness(vecs.detach(), mask, img, order, alpha, eps)
+        ctx.save_for_backward(vecs, rec)
+        ctx.guides = (mask, img, order, alpha, eps)
+        return _smoothness.mean_of(rec)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        vecs, rec = ctx.saved_tensors
+        mask, img, order, alpha, eps = ctx.guides
+        scale = (g.to(rec.device, torch.float64) / (rec[:, 0] + rec[:, 1])).to(torch.float32)      # on the device: nothing is read back
+        grad = _smoothness.flow_smoothness_grad(vecs.detach(), mask, img, order, alpha, eps, scale)
+        return _reduce_to(grad, vecs), None, None, None, None, None

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _consistency, _native, distributed
+from . import _consistency, _native, _smoothness, distributed
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
@@ -1311,6 +1311,80 @@ class Flow(object):
             if not any(f & (_native.FLAG_NZ_MASKED | _native.FLAG_NZ_THR_MASKED) for f in word):
                 out._flag_cache = (out._key(), word)
         return out
+
+    # ------------------------------------------------------------------------------------------
+    # edge-aware smoothness (an extension: the reference has no such methods)
+    # ------------------------------------------------------------------------------------------
+    def _smoothness_operands(self, img, order, alpha, eps, consider_mask: bool):
+        """The checks the three smoothness methods share; returns the arguments of `_smoothness.flow_smoothness` up to eps."""
+        err = "Error computing flow smoothness: "
+        if img is not None:
+            if isinstance(img, np.ndarray):
+                if img.dtype not in (np.float32, np.uint8):
+                    raise TypeError(err + "Img needs to be of dtype float32 or uint8")
+                img = torch.from_numpy(img)
+            if not isinstance(img, torch.Tensor):
+                raise TypeError(err + "Img needs to be a torch tensor or a numpy array")
+            if img.dtype not in (torch.float32, torch.uint8):
+                raise TypeError(err + "Img needs to be of dtype float32 or uint8")
+            if img.dim() not in (3, 4):
+                raise ValueError(err + "Img needs to have 3 or 4 dimensions, C-H-W or N-C-H-W")
+            if not 1 <= img.shape[-3] <= 4:
+                raise ValueError(err + "Img needs to have 1 to 4 channels")
+            if tuple(img.shape[-2:]) != tuple(self.shape[1:]):
+                raise ValueError(err + "Img needs to have the H-W shape of the flow")
+            if img.dim() == 4 and img.shape[0] != self.shape[0]:
+                raise ValueError(err + "Img needs to have the batch size of the flow")
+        order = 1 if order is None else order
+        if not isinstance(order, int) or isinstance(order, bool):
+            raise TypeError(err + "Order needs to be an integer")
+        if order not in (1, 2):
+            raise ValueError(err + "Order needs to be 1 or 2")
+        alpha = 10.0 if alpha is None else alpha
+        eps = 0.001 if eps is None else eps
+        for name, value in (("Alpha", alpha), ("Eps", eps)):
+            if not isinstance(value, (int, float)) or isinstance(value, bool):
+                raise TypeError(err + name + " needs to be an integer or a float")
+            if not (math.isfinite(value) and value >= 0):
+                raise ValueError(err + name + " needs to be finite and not negative")
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError(err + "Consider_mask needs to be boolean")
+        if img is not None:
+            img = img.detach()
+            if img.device != self._device:
+                img = img.to(self._device)
+            img = img.contiguous()
+        return self._fv, (self._mask if consider_mask else None), img, order, float(alpha), float(eps)
+
+    def smoothness_stats(self, img=None, order: int = None, alpha: float = None, eps: float = None, consider_mask: bool = None) -> dict:
+        """The edge-aware smoothness penalty of this flow, per batch element.  A term is a first (`order` 1, the default) or second
+        (`order` 2) difference d of the vectors along x or along y, penalised as sqrt(du^2 + eps^2) + sqrt(dv^2 + eps^2) (`eps`
+        default 0.001) and, with a guidance image `img` (tensor or array, float32 or uint8 read as s / 255, C-H-W or N-C-H-W with 1 to 4
+        channels), weighted by exp(-alpha g) (`alpha` default 10), g being the mean over the channels of the absolute image difference
+        across the same pixels.  A term counts where every pixel it reads is valid in the mask (every term that exists if
+        `consider_mask` is False).  Returns a dict of tensors on the flow's device: 'count_x', 'count_y' int64 [N]; 'sum_x', 'sum_y',
+        'max' float64 [N]; 'smoothness' float64 [N], (sum_x + sum_y) / (count_x + count_y), NaN without a valid term.  One pass of
+        ofl_smoothness.hip, float64 sums in a fixed order (bitwise reproducible, independent of the batch); nothing is
+        read back to the host.  Not differentiable: see :meth:`smoothness`."""
+        rec, _ = _smoothness.flow_smoothness(*self._smoothness_operands(img, order, alpha, eps, consider_mask))
+        rec = rec.to(self._device)
+        return {'count_x': rec[:, 0].to(torch.int64), 'count_y': rec[:, 1].to(torch.int64), 'sum_x': rec[:, 2].clone(),
+                'sum_y': rec[:, 3].clone(), 'max': rec[:, 4].clone(), 'smoothness': (rec[:, 2] + rec[:, 3]) / (rec[:, 0] + rec[:, 1])}
+
+    def smoothness_map(self, img=None, order: int = None, alpha: float = None, eps: float = None, consider_mask: bool = None) -> torch.Tensor:
+        """The x term plus the y term of :meth:`smoothness_stats` at every pixel: float32 N-H-W on the flow's device, a term being
+        attributed to its left / upper pixel (order 1) or its centre pixel (order 2); a term that is not valid is 0.  Not
+        differentiable: see :meth:`smoothness`."""
+        ops = self._smoothness_operands(img, order, alpha, eps, consider_mask)
+        return _smoothness.flow_smoothness(*ops, want_map=True)[1].to(self._device)
+
+    def smoothness(self, img=None, order: int = None, alpha: float = None, eps: float = None, consider_mask: bool = None) -> torch.Tensor:
+        """The mean of the valid terms of :meth:`smoothness_stats` per batch element: float32 [N] on the flow's device (the float64
+        quotient rounded once; NaN for an element without a valid term).  Differentiable with respect to the flow vectors ONLY -- the
+        smoothness term of an unsupervised flow loss.  The image is guidance and carries no gradient, even if it requires one; an
+        element without a valid term has gradient 0.  The backward pass gathers (no atomics): it is bitwise reproducible."""
+        return _smoothness.smoothness(*self._smoothness_operands(img, order, alpha, eps, consider_mask)).to(self._device)
 
     # ------------------------------------------------------------------------------------------
     # composition (flow_class.py:1648-1810)

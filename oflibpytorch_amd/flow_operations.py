@@ -101,6 +101,21 @@ def flow_consistency(flow, back, ref: str, mask=None, back_mask=None, alpha: flo
     return res if len(flow.shape) > 3 else {k: v.squeeze(0) for k, v in res.items()}
 
 
+def flow_smoothness(flow, img=None, mask=None, order: int = None, alpha: float = None, eps: float = None) -> torch.Tensor:
+    """Flow(flow, mask=mask).smoothness(img, order, alpha, eps): the edge-aware smoothness loss, float32 [N] (a scalar tensor for 3-D
+    input), differentiable with respect to a tensor `flow`.  An extension: the reference has no such function."""
+    s = Flow(flow, 't', mask).smoothness(img, order=order, alpha=alpha, eps=eps)
+    return s if len(flow.shape) > 3 else s.squeeze(0)
+
+
+def flow_smoothness_stats(flow, img=None, mask=None, order: int = None, alpha: float = None, eps: float = None) -> dict:
+    """Flow(flow, mask=mask).smoothness_stats(img, order, alpha, eps): the dict of Flow.smoothness_stats for arrays / tensors
+    (N-)2-H-W or (N-)H-W-2 with an optional mask (N-)H-W; 3-D in -> entries without the batch dimension.  An extension (DESIGN.md
+    3.19)."""
+    stats = Flow(flow, 't', mask).smoothness_stats(img, order=order, alpha=alpha, eps=eps)
+    return stats if len(flow.shape) > 3 else {k: v.squeeze(0) for k, v in stats.items()}
+
+
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
     """Concatenate flow objects of equal H, W, ref and device along the batch axis (flow_operations.py:458-483)"""
     if not isinstance(flows, (list, tuple)):
