@@ -938,6 +938,57 @@ int ofl_flow_smoothness_grad_f32(const void* flow, int64_t flow_bs, int32_t flow
                                  const void* img, int64_t img_bs, int32_t img_channels, int32_t img_u8, int32_t order, float alpha,
                                  float eps, const float* scale, float* grad, int32_t n, int32_t h, int32_t w, void* stream);
 
+/*
+ * The photometric term of an unsupervised flow loss, warp and comparison in one pass (which defines the numbers;
+ * ofl_photometric.hip): Flow.photometric / photometric_map / photometric_stats.  An extension: the reference has no such function.
+ * `img` is the frame on the flow's own grid, `other` the frame the flow points into; flow_sign -1 for 's' flows (the sample of pixel p
+ * lies at p + a(p)), +1 for 't' flows (at p - a(p)).  Per pixel p, every step fp32 with one rounding per operation (the fused
+ * multiply-adds are those of the backward warp):
+ *   Iw_c, mr   plane c of `other` and the insideness of its taps sampled bilinearly at unnormalise(grid - flow_sign a), in the
+ *              expressions of ofl_warp_bwd_f32: a tap outside the frame reads as 0
+ *   known      (mr > 0.99999f) and mask (a NULL mask is all True); a non-finite vector fails the comparisons: not known
+ *   d_c        Iw_c - I_c(p);  r_c = sqrt(d_c d_c + eps eps), the root correctly rounded
+ *   rho        (((r_0 + r_1) + ...)) / float(C): channels added in ascending order, one division; +0.0f where the pixel is not known
+ * flow [*,2,H,W] fp32 (half = 0) or fp16 (1: up-converted in registers, exact), flow_bs elements between images (0 broadcasts one
+ * image); mask optional [*,H,W] bytes (any non-zero byte is True), mask_bs bytes between images; img, other [*,C,H,W], 1 <= C <= 4, both
+ * fp32 (img_u8 = 0) or both uint8 (1: a sample s is float(s) / 255.0f), img_bs / other_bs elements between images (0 broadcasts one
+ * image).  Inputs are never written.  The warped image is never written.
+ *
+ * ofl_flow_photometric_workspace_bytes(n, h, w): bytes of the workspace of ofl_flow_photometric_f64 (8-byte aligned; every word the
+ *   second launch reads is written by the first: nothing to clear), or OFL_E_ARG for sizes that call rejects.
+ *
+ * ofl_flow_photometric_f64: records (optional) float64 [n, OFL_PHOTOMETRIC_RECORD], per image over its known pixels
+ *     [0] count   [1] sum rho   [2] max rho (0 without a known pixel)   [3 .. 7] 0.
+ *   The count is exact.  The sum is the float64 sum of the fp32 rho in a fixed order -- a lane's pixels ascending, the lanes of a wave
+ *   by a butterfly, the waves and then the blocks of an image in index order -- and the number of blocks depends on (h, w) only: no
+ *   float atomics, an image's record has the same bits in any batch and on any run.  photometric_map (optional) fp32 [n,h,w]: rho.  At
+ *   least one of the two must be given; the workspace is needed (and touched) only with records.  Every element of every output given
+ *   is WRITTEN.  One launch, two with records: ofl_last_kernel_name() then names flow_photometric_finish_kernel.
+ *
+ * ofl_flow_photometric_grad_f32: the backward of the per-image mean sum / count with respect to the flow vectors.  scale fp32 [n] DEVICE
+ *   memory (the upstream gradient / count); grad fp32 [n,2,h,w], every element written.  A known pixel recomputes the fp32 d_c of the
+ *   forward; then, in float64: q_c = double(d_c) / sqrt(double(d_c)^2 + double(eps)^2), 0 where the root is 0;
+ *   gx_c = sum_j sgn_j fr_j double(v_j,c) over the taps nw, ne, sw, se inside the frame, sgn -1 for west and +1 for east taps, fr the other
+ *   axis's weight, from the fractions double(sx) - double(floorf(sx)) and their complements to 1; gy_c likewise (north -1, south +1).
+ *   grad_u(p) = float(double(scale) * (-flow_sign) * (((q_0 gx_0 + q_1 gx_1) + ...) / double(C))), grad_v with gy; exactly 0 where the
+ *   pixel is not known (so an image without a known pixel, whose scale is not finite, has gradient 0).  The kernel gathers: no scatter,
+ *   no atomics.  The images carry no gradient.
+ *
+ * OFL_E_ARG, before any launch, for: n outside 1 .. 65535, h or w < 2, h * w >= 2^31, a flow_sign other than +-1, C outside 1 .. 4, eps
+ * negative or not finite, a NULL flow, img, other, scale or grad pointer, map and records both NULL, records without a workspace, a
+ * negative stride, a flag that is neither 0 nor 1, a pointer not aligned to its element (workspace, records: 8 bytes).
+ */
+#define OFL_PHOTOMETRIC_RECORD 8
+int64_t ofl_flow_photometric_workspace_bytes(int32_t n, int32_t h, int32_t w);
+int ofl_flow_photometric_f64(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, const void* img,
+                             int64_t img_bs, const void* other, int64_t other_bs, int32_t channels, int32_t img_u8, float flow_sign,
+                             float eps, void* workspace, float* photometric_map, double* records, int32_t n, int32_t h, int32_t w,
+                             void* stream);
+int ofl_flow_photometric_grad_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
+                                  const void* img, int64_t img_bs, const void* other, int64_t other_bs, int32_t channels, int32_t img_u8,
+                                  float flow_sign, float eps, const float* scale, float* grad, int32_t n, int32_t h, int32_t w,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

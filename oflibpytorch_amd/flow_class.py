@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _consistency, _native, _smoothness, distributed
+from . import _consistency, _native, _photometric, _smoothness, distributed
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
@@ -1385,6 +1385,86 @@ class Flow(object):
         smoothness term of an unsupervised flow loss.  The image is guidance and carries no gradient, even if it requires one; an
         element without a valid term has gradient 0.  The backward pass gathers (no atomics): it is bitwise reproducible."""
         return _smoothness.smoothness(*self._smoothness_operands(img, order, alpha, eps, consider_mask)).to(self._device)
+
+    # ------------------------------------------------------------------------------------------
+    # photometric loss (DESIGN.md 3.20; an extension: the reference has no such methods)
+    # ------------------------------------------------------------------------------------------
+    def _photometric_operands(self, img, other, eps, consider_mask: bool):
+        """The checks the three photometric methods share; returns the arguments of `_photometric.flow_photometric` up to eps."""
+        err = "Error computing photometric loss: "
+        images = []
+        for name, im in (("Img", img), ("Other", other)):
+            if isinstance(im, np.ndarray):
+                if im.dtype not in (np.float32, np.uint8):
+                    raise TypeError(err + name + " needs to be of dtype float32 or uint8")
+                im = torch.from_numpy(im)
+            if not isinstance(im, torch.Tensor):
+                raise TypeError(err + name + " needs to be a torch tensor or a numpy array")
+            if im.dtype not in (torch.float32, torch.uint8):
+                raise TypeError(err + name + " needs to be of dtype float32 or uint8")
+            images.append(im)
+        img, other = images
+        if img.dtype != other.dtype:
+            raise TypeError(err + "Img and other need to be of the same dtype")
+        for name, im in (("Img", img), ("Other", other)):
+            if im.dim() not in (3, 4):
+                raise ValueError(err + name + " needs to have 3 or 4 dimensions, C-H-W or N-C-H-W")
+            if not 1 <= im.shape[-3] <= 4:
+                raise ValueError(err + name + " needs to have 1 to 4 channels")
+        if img.shape[-3] != other.shape[-3]:
+            raise ValueError(err + "Img and other need to have the same number of channels")
+        for name, im in (("Img", img), ("Other", other)):
+            if tuple(im.shape[-2:]) != tuple(self.shape[1:]):
+                raise ValueError(err + name + " needs to have the H-W shape of the flow")
+            if im.dim() == 4 and im.shape[0] != self.shape[0]:
+                raise ValueError(err + name + " needs to have the batch size of the flow")
+        if self.shape[1] < 2 or self.shape[2] < 2:
+            raise ValueError(err + "Flow field needs to be at least 2 pixels high and wide")
+        eps = 0.001 if eps is None else eps
+        if not isinstance(eps, (int, float)) or isinstance(eps, bool):
+            raise TypeError(err + "Eps needs to be an integer or a float")
+        if not (math.isfinite(eps) and eps >= 0):
+            raise ValueError(err + "Eps needs to be finite and not negative")
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError(err + "Consider_mask needs to be boolean")
+        images = []
+        for im in (img, other):
+            im = im.detach()
+            if im.device != self._device:
+                im = im.to(self._device)
+            images.append(im.contiguous())
+        return (self._fv, (self._mask if consider_mask else None), images[0], images[1], -1.0 if self._ref == 's' else 1.0,
+                float(eps))
+
+    def photometric_stats(self, img, other, eps: float = None, consider_mask: bool = None) -> dict:
+        """The photometric penalty of this flow between two frames, per batch element.  `img` is the frame on the flow's own grid,
+        `other` the frame the flow points into: for an 's' flow from frame 1 to frame 2, `img` is frame 1 and `other` frame 2; for a
+        't' flow, `img` is frame 2 and `other` frame 1.  Both are tensors or arrays of one dtype, float32 or uint8 (read as s / 255),
+        C-H-W or N-C-H-W with the same 1 to 4 channels.  `other` is sampled bilinearly where the flow points -- at p + self(p) for 's'
+        flows, at p - self(p) for 't' flows, the arithmetic of :meth:`apply` on a 't' flow -- and compared with `img` under the
+        Charbonnier penalty sqrt(d^2 + eps^2) (`eps` default 0.001), averaged over the channels.  A pixel is KNOWN where the sample's
+        taps lie in the frame and the pixel is valid in this flow's mask (with `consider_mask` False: the frame test alone).  Returns a
+        dict of tensors on the flow's device: 'count' int64 [N], the known pixels; 'sum', 'max' float64 [N] over them; 'photometric'
+        float64 [N], sum / count, NaN without a known pixel.  One pass of ofl_photometric.hip: the warped image is never written,
+        float64 sums in a fixed order (bitwise reproducible, independent of the batch), nothing is read back to the
+        host.  Not differentiable: see :meth:`photometric`."""
+        rec, _ = _photometric.flow_photometric(*self._photometric_operands(img, other, eps, consider_mask))
+        rec = rec.to(self._device)
+        return {'count': rec[:, 0].to(torch.int64), 'sum': rec[:, 1].clone(), 'max': rec[:, 2].clone(), 'photometric': rec[:, 1] / rec[:, 0]}
+
+    def photometric_map(self, img, other, eps: float = None, consider_mask: bool = None) -> torch.Tensor:
+        """The penalty of :meth:`photometric_stats` at every pixel: float32 N-H-W on the flow's device, 0 where the pixel is not
+        known (the kernel writes nothing else).  Not differentiable: see :meth:`photometric`."""
+        ops = self._photometric_operands(img, other, eps, consider_mask)
+        return _photometric.flow_photometric(*ops, want_map=True, want_record=False)[1].to(self._device)
+
+    def photometric(self, img, other, eps: float = None, consider_mask: bool = None) -> torch.Tensor:
+        """The mean of :meth:`photometric_stats` over the known pixels per batch element: float32 [N] on the flow's device (the
+        float64 quotient rounded once; NaN for an element without a known pixel).  Differentiable with respect to the flow vectors
+        ONLY -- the photometric term of an unsupervised flow loss.  The images carry no gradient, even if they require one; an
+        element without a known pixel has gradient 0.  The backward pass gathers (no atomics): it is bitwise reproducible."""
+        return _photometric.photometric(*self._photometric_operands(img, other, eps, consider_mask)).to(self._device)
 
     # ------------------------------------------------------------------------------------------
     # composition (flow_class.py:1648-1810)

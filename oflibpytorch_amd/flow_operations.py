@@ -116,6 +116,21 @@ def flow_smoothness_stats(flow, img=None, mask=None, order: int = None, alpha: f
     return stats if len(flow.shape) > 3 else {k: v.squeeze(0) for k, v in stats.items()}
 
 
+def flow_photometric(flow, img, other, ref: str, mask=None, eps: float = None) -> torch.Tensor:
+    """Flow(flow, ref, mask).photometric(img, other, eps): the photometric loss between the frame `img` on the flow's grid and the
+    frame `other` it points into, float32 [N] (a scalar tensor for 3-D input), differentiable with respect to a tensor `flow`.  An
+    extension: the reference has no such function."""
+    p = Flow(flow, ref, mask).photometric(img, other, eps=eps)
+    return p if len(flow.shape) > 3 else p.squeeze(0)
+
+
+def flow_photometric_stats(flow, img, other, ref: str, mask=None, eps: float = None) -> dict:
+    """Flow(flow, ref, mask).photometric_stats(img, other, eps): the dict of Flow.photometric_stats for arrays / tensors (N-)2-H-W or
+    (N-)H-W-2 with an optional mask (N-)H-W; 3-D in -> entries without the batch dimension.  An extension."""
+    stats = Flow(flow, ref, mask).photometric_stats(img, other, eps=eps)
+    return stats if len(flow.shape) > 3 else {k: v.squeeze(0) for k, v in stats.items()}
+
+
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
     """Concatenate flow objects of equal H, W, ref and device along the batch axis (flow_operations.py:458-483)"""
     if not isinstance(flows, (list, tuple)):
