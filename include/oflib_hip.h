@@ -989,6 +989,59 @@ int ofl_flow_photometric_grad_f32(const void* flow, int64_t flow_bs, int32_t flo
                                   float flow_sign, float eps, const float* scale, float* grad, int32_t n, int32_t h, int32_t w,
                                   void* stream);
 
+/*
+ * The census data term of an unsupervised flow loss, warp and comparison of soft ternary census signatures in one pass (DESIGN.md
+ * 3.21, which defines the numbers; ofl_census.hip): Flow.census / census_map / census_stats.  An extension: the reference has no such
+ * function.  `img`, `other` and flow_sign as for ofl_flow_photometric_f64.  patch is 3, 5 or 7, R = patch / 2.  Every step fp32 with one
+ * rounding per operation unless it says float64:
+ *   Iw_c, mr   as in ofl_flow_photometric_f64, except that a uint8 sample s is read as float(s), on the scale 0 .. 255
+ *   grey       g = v_0 for C = 1, (0.299f v_0 + 0.587f v_1) + 0.114f v_2 for C = 3;  G = 255.0f g for fp32 images, G = g for uint8.
+ *              Gw(p) is the grey of Iw (the channels are warped, then combined), Gi(p) the grey of img
+ *   usable(p)  p in the frame, mask(p) (a NULL mask is all True), mr(p) > 0.99999f
+ *   U(p), n    the offsets o != 0 of the patch around p with usable(p + o), and their number;  known(p) = usable(p) and n >= 1.  There
+ *              is no border rule: a neighbour that is not usable is no term
+ *   per term   o in U(p), dy ascending and dx ascending within it:  dW = Gw(p+o) - Gw(p), tw = dW / sqrtf(0.81f + dW dW), ti likewise
+ *              from Gi, e = ti - tw, s = e e, f = s / (thresh + s)
+ *   per pixel  hd = (sum of f in that order) / float(n), b = hd + eps, rho = float(pow(double(b), double(q))): the float64 pow rounded
+ *              once; +0.0f where the pixel is not known
+ * flow, mask, img, other, their strides and flags as for ofl_flow_photometric_f64, with C = 1 or 3.  Inputs are never written; neither
+ * the warped image nor any tensor of patch^2 - 1 channels is.
+ *
+ * ofl_flow_census_workspace_bytes(n, h, w, patch): bytes of the workspace of ofl_flow_census_f64 (8-byte aligned; every word the
+ *   second launch reads is written by the first: nothing to clear), or OFL_E_ARG for sizes that call rejects.
+ *
+ * ofl_flow_census_f64: records (optional) float64 [n, OFL_CENSUS_RECORD], per image over its known pixels
+ *     [0] count   [1] sum rho   [2] max rho (0 without a known pixel)   [3] sum n(p)   [4 .. 7] 0.
+ *   [0] and [3] are exact.  The sum is the float64 sum of the fp32 rho in a fixed order -- a lane's pixels ascending, the lanes of a
+ *   wave by a butterfly, the waves and then the blocks of an image in index order -- and the number of blocks depends on (h, w) only:
+ *   no float atomics, an image's record has the same bits in any batch and on any run.  census_map (optional) fp32 [n,h,w]: rho.  At
+ *   least one of the two must be given; the workspace is needed (and touched) only with records.  Every element of every output given
+ *   is WRITTEN.  One launch, two with records: ofl_last_kernel_name() then names flow_census_finish_kernel.
+ *
+ * ofl_flow_census_grad_f32: the backward of the per-image mean sum / count with respect to the flow vectors.  scale fp32 [n] DEVICE
+ *   memory (the upstream gradient / count); grad fp32 [n,2,h,w], every element written.  In float64 on the fp32 Gw, Gi and b of the
+ *   forward: kappa(p) = q b(p)^(q-1) / n(p) where p is known, k_o(p) = thresh / (thresh + s)^2 (-2 e) 0.81 / (0.81 + dW^2)^(3/2),
+ *     dL/dGw(x) = scale ( sum over known p with x - p in U(p) of kappa(p) k_{x-p}(p)  -  [x known] kappa(x) sum over o in U(x) of k_o(x) ),
+ *   grad_u(x) = float(dL/dGw(x) (-flow_sign) S sum_c g_c gx_c(x)) with S = 255 for fp32 images and 1 for uint8, g_c the grey weight
+ *   (1 for C = 1) and gx_c, gy_c as in ofl_flow_photometric_grad_f32; exactly 0 where the pixel is not known.  One launch that
+ *   recomputes kappa over a halo: no workspace, no scatter, no atomics.  The images carry no gradient.
+ *
+ * OFL_E_ARG, before any launch, for: n outside 1 .. 65535, h or w < 2, h * w >= 2^31, a flow_sign other than +-1, C other than 1 or 3,
+ * a patch other than 3, 5 or 7, thresh or eps not positive or not finite, q outside (0, 1], a NULL flow, img, other, scale or grad
+ * pointer, map and records both NULL, records without a workspace, a negative stride, a flag that is neither 0 nor 1, a pointer not
+ * aligned to its element (workspace, records: 8 bytes).
+ */
+#define OFL_CENSUS_RECORD 8
+int64_t ofl_flow_census_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t patch);
+int ofl_flow_census_f64(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, const void* img,
+                        int64_t img_bs, const void* other, int64_t other_bs, int32_t channels, int32_t img_u8, float flow_sign,
+                        int32_t patch, float thresh, float eps, float q, void* workspace, float* census_map, double* records, int32_t n,
+                        int32_t h, int32_t w, void* stream);
+int ofl_flow_census_grad_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, const void* img,
+                             int64_t img_bs, const void* other, int64_t other_bs, int32_t channels, int32_t img_u8, float flow_sign,
+                             int32_t patch, float thresh, float eps, float q, const float* scale, float* grad, int32_t n, int32_t h,
+                             int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ implemented (`once_differentiable` raises).
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _native, _photometric, _smoothness
+from . import _census, _native, _photometric, _smoothness
 
 
 def _reduce_to(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
@@ -278,3 +278,27 @@ class PhotometricFn(torch.autograd.Function):
         scale = (g.to(rec.device, torch.float64) / rec[:, 0]).to(torch.float32)                      # on the device: nothing is read back
         grad = _photometric.flow_photometric_grad(vecs.detach(), mask, img, other, flow_sign, eps, scale)
         return _reduce_to(grad, vecs), None, None, None, None, None
+
+
+class CensusFn(torch.autograd.Function):
+    """census[n] = mean over the known pixels of the census penalty between `img` and `other` sampled where the flow points
+    (Flow.census): fp32, rounded once from the float64 quotient of the kernel's sum and count; NaN for an image without
+    a known pixel, whose gradient is 0.  Differentiable with respect to the vectors only: the images carry no gradient.  An fp16-stored
+    flow is saved as it is stored."""
+
+    @staticmethod
+    def forward(ctx, vecs, mask, img, other, flow_sign, patch, thresh, eps, q):
+        img, other = img.detach(), other.detach()
+        rec, _ = _census.flow_census(vecs.detach(), mask, img, other, flow_sign, patch, thresh, eps, q)
+        ctx.save_for_backward(vecs, mask, img, other, rec)
+        ctx.params = (flow_sign, patch, thresh, eps, q)
+        return _census.mean_of(rec)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        vecs, mask, img, other, rec = ctx.saved_tensors
+        flow_sign, patch, thresh, eps, q = ctx.params
+        scale = (g.to(rec.device, torch.float64) / rec[:, 0]).to(torch.float32)                      # on the device: nothing is read back
+        grad = _census.flow_census_grad(vecs.detach(), mask, img, other, flow_sign, patch, thresh, eps, q, scale)
+        return _reduce_to(grad, vecs), None, None, None, None, None, None, None, None

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _consistency, _native, _photometric, _smoothness, distributed
+from . import _census, _consistency, _native, _photometric, _smoothness, distributed
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
@@ -1465,6 +1465,105 @@ class Flow(object):
         ONLY -- the photometric term of an unsupervised flow loss.  The images carry no gradient, even if they require one; an
         element without a known pixel has gradient 0.  The backward pass gathers (no atomics): it is bitwise reproducible."""
         return _photometric.photometric(*self._photometric_operands(img, other, eps, consider_mask)).to(self._device)
+
+    # ------------------------------------------------------------------------------------------
+    # census loss (DESIGN.md 3.21; an extension: the reference has no such methods)
+    # ------------------------------------------------------------------------------------------
+    def _census_operands(self, img, other, patch, thresh, eps, q, consider_mask: bool):
+        """The checks the three census methods share; returns the arguments of `_census.flow_census` up to q."""
+        err = "Error computing census loss: "
+        images = []
+        for name, im in (("Img", img), ("Other", other)):
+            if isinstance(im, np.ndarray):
+                if im.dtype not in (np.float32, np.uint8):
+                    raise TypeError(err + name + " needs to be of dtype float32 or uint8")
+                im = torch.from_numpy(im)
+            if not isinstance(im, torch.Tensor):
+                raise TypeError(err + name + " needs to be a torch tensor or a numpy array")
+            if im.dtype not in (torch.float32, torch.uint8):
+                raise TypeError(err + name + " needs to be of dtype float32 or uint8")
+            images.append(im)
+        img, other = images
+        if img.dtype != other.dtype:
+            raise TypeError(err + "Img and other need to be of the same dtype")
+        for name, im in (("Img", img), ("Other", other)):
+            if im.dim() not in (3, 4):
+                raise ValueError(err + name + " needs to have 3 or 4 dimensions, C-H-W or N-C-H-W")
+            if im.shape[-3] not in (1, 3):
+                raise ValueError(err + name + " needs to have 1 or 3 channels")
+        if img.shape[-3] != other.shape[-3]:
+            raise ValueError(err + "Img and other need to have the same number of channels")
+        for name, im in (("Img", img), ("Other", other)):
+            if tuple(im.shape[-2:]) != tuple(self.shape[1:]):
+                raise ValueError(err + name + " needs to have the H-W shape of the flow")
+            if im.dim() == 4 and im.shape[0] != self.shape[0]:
+                raise ValueError(err + name + " needs to have the batch size of the flow")
+        if self.shape[1] < 2 or self.shape[2] < 2:
+            raise ValueError(err + "Flow field needs to be at least 2 pixels high and wide")
+        patch = _census.PATCH if patch is None else patch
+        if not isinstance(patch, int) or isinstance(patch, bool):
+            raise TypeError(err + "Patch needs to be an integer")
+        if patch not in (3, 5, 7):
+            raise ValueError(err + "Patch needs to be 3, 5 or 7")
+        values = []
+        for name, val, default in (("Thresh", thresh, _census.THRESH), ("Eps", eps, _census.EPS), ("Q", q, _census.Q)):
+            val = default if val is None else val
+            if not isinstance(val, (int, float)) or isinstance(val, bool):
+                raise TypeError(err + name + " needs to be an integer or a float")
+            # (the kernels take float32: a value that rounds to 0 or to infinity there is out of range)
+            if not (math.isfinite(val) and val > 0 and 0 < float(np.float32(val)) < float('inf')):
+                raise ValueError(err + name + " needs to be finite and larger than 0")
+            values.append(float(val))
+        if values[2] > 1:
+            raise ValueError(err + "Q needs to be at most 1")
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError(err + "Consider_mask needs to be boolean")
+        images = []
+        for im in (img, other):
+            im = im.detach()
+            if im.device != self._device:
+                im = im.to(self._device)
+            images.append(im.contiguous())
+        return (self._fv, (self._mask if consider_mask else None), images[0], images[1], -1.0 if self._ref == 's' else 1.0,
+                patch, values[0], values[1], values[2])
+
+    def census_stats(self, img, other, patch: int = None, thresh: float = None, eps: float = None, q: float = None,
+                     consider_mask: bool = None) -> dict:
+        """The census penalty of this flow between two frames, per batch element: the data term unsupervised flow training uses in
+        place of a brightness difference, because it survives a change of illumination.  `img` is the frame on the flow's own grid,
+        `other` the frame the flow points into, as in :meth:`photometric_stats`: tensors or arrays of one dtype, float32 (scale 0 .. 1)
+        or uint8, C-H-W or N-C-H-W with the same 1 or 3 channels.  `other` is sampled bilinearly where the flow points, both frames
+        are turned into grey on the scale 0 .. 255, and for every neighbour o of a pixel p in its `patch` x `patch` window (3, 5 or
+        7, default 7) the soft signs t = d / sqrt(0.81 + d^2) of the grey differences d = G(p + o) - G(p) are compared:
+        f = (ti - tw)^2 / (`thresh` + (ti - tw)^2), `thresh` default 0.1.  The penalty of p is (mean of f + `eps`)^`q`, `eps` default
+        0.01, `q` default 0.4.  A pixel is USABLE where it is valid in this flow's mask (with `consider_mask` False: everywhere) and
+        its sample's taps lie in the frame; only usable neighbours are terms, and a pixel is KNOWN where it is usable and has at
+        least one.  Returns a dict of tensors on the flow's device: 'count' int64 [N], the known pixels; 'sum', 'max' float64 [N]
+        over them; 'census' float64 [N], sum / count, NaN without a known pixel; 'fill' float64 [N], the share of the patch
+        neighbours of the known pixels that were terms.  One pass of ofl_census.hip from LDS tiles: neither the warped image nor a
+        tensor of patch^2 - 1 channels is written, float64 sums in a fixed order (bitwise reproducible, independent of the batch;
+        DESIGN.md 3.21), nothing is read back to the host.  Not differentiable: see :meth:`census`."""
+        ops = self._census_operands(img, other, patch, thresh, eps, q, consider_mask)
+        rec, _ = _census.flow_census(*ops)
+        rec = rec.to(self._device)
+        return {'count': rec[:, 0].to(torch.int64), 'sum': rec[:, 1].clone(), 'max': rec[:, 2].clone(), 'census': rec[:, 1] / rec[:, 0],
+                'fill': rec[:, 3] / (rec[:, 0] * float(ops[5] * ops[5] - 1))}
+
+    def census_map(self, img, other, patch: int = None, thresh: float = None, eps: float = None, q: float = None,
+                   consider_mask: bool = None) -> torch.Tensor:
+        """The penalty of :meth:`census_stats` at every pixel: float32 N-H-W on the flow's device, 0 where the pixel is not known
+        (the kernel writes nothing else).  Not differentiable: see :meth:`census`."""
+        ops = self._census_operands(img, other, patch, thresh, eps, q, consider_mask)
+        return _census.flow_census(*ops, want_map=True, want_record=False)[1].to(self._device)
+
+    def census(self, img, other, patch: int = None, thresh: float = None, eps: float = None, q: float = None,
+               consider_mask: bool = None) -> torch.Tensor:
+        """The mean of :meth:`census_stats` over the known pixels per batch element: float32 [N] on the flow's device (the float64
+        quotient rounded once; NaN for an element without a known pixel).  Differentiable with respect to the flow vectors ONLY --
+        the census term of an unsupervised flow loss.  The images carry no gradient, even if they require one; an element without a
+        known pixel has gradient 0.  The backward pass gathers (no atomics): it is bitwise reproducible."""
+        return _census.census(*self._census_operands(img, other, patch, thresh, eps, q, consider_mask)).to(self._device)
 
     # ------------------------------------------------------------------------------------------
     # composition (flow_class.py:1648-1810)

@@ -131,6 +131,24 @@ def flow_photometric_stats(flow, img, other, ref: str, mask=None, eps: float = N
     return stats if len(flow.shape) > 3 else {k: v.squeeze(0) for k, v in stats.items()}
 
 
+def flow_census(flow, img, other, ref: str, mask=None, patch: int = None, thresh: float = None, eps: float = None,
+                q: float = None) -> torch.Tensor:
+    """Flow(flow, ref, mask).census(img, other, patch, thresh, eps, q): the census loss between the frame `img` on the flow's grid and
+    the frame `other` it points into, float32 [N] (a scalar tensor for 3-D input), differentiable with respect to a tensor `flow`.  An
+    extension: the reference has no such function."""
+    c = Flow(flow, ref, mask).census(img, other, patch=patch, thresh=thresh, eps=eps, q=q)
+    return c if len(flow.shape) > 3 else c.squeeze(0)
+
+
+def flow_census_stats(flow, img, other, ref: str, mask=None, patch: int = None, thresh: float = None, eps: float = None,
+                      q: float = None) -> dict:
+    """Flow(flow, ref, mask).census_stats(img, other, patch, thresh, eps, q): the dict of Flow.census_stats for arrays / tensors
+    (N-)2-H-W or (N-)H-W-2 with an optional mask (N-)H-W; 3-D in -> entries without the batch dimension.  An extension (DESIGN.md
+    3.21)."""
+    stats = Flow(flow, ref, mask).census_stats(img, other, patch=patch, thresh=thresh, eps=eps, q=q)
+    return stats if len(flow.shape) > 3 else {k: v.squeeze(0) for k, v in stats.items()}
+
+
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
     """Concatenate flow objects of equal H, W, ref and device along the batch axis (flow_operations.py:458-483)"""
     if not isinstance(flows, (list, tuple)):
