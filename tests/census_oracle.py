@@ -10,7 +10,6 @@ fractions and the inside tests of `grad_oracle64.warp_taps`; next to it `grad` r
 contributions (they can cancel, so a bound on the gradient's error is relative to A, not to the gradient).
 """
 import functools
-import math
 
 import numpy as np
 import torch
@@ -18,6 +17,7 @@ import torch
 import grad_oracle64 as go
 import oracle_backend as ob
 import photometric_oracle as po
+import special_values as sv
 
 F32, F64 = np.float32, np.float64
 PATCHES = (3, 5, 7)
@@ -101,7 +101,7 @@ def compute(a, mask, img, other, ref, patch=PATCH, thresh=THRESH, eps=EPS, q=Q):
     rec = np.zeros((n, 8), F64)
     for i in range(n):
         vals = rho[i][known[i]].astype(F64)
-        rec[i, :4] = [vals.size, math.fsum(vals.tolist()), vals.max() if vals.size else 0.0, cnt[i][known[i]].sum()]
+        rec[i, :4] = [vals.size, sv.record_sum(vals), sv.record_max(vals), cnt[i][known[i]].sum()]
     with np.errstate(invalid='ignore', divide='ignore'):
         loss = (rec[:, 1] / rec[:, 0]).astype(F32)
     return {'map': cmap, 'known': known, 'usable': usable, 'inside': inside, 'n': cnt, 'hd': hd, 'b': b, 'gw': gw, 'gi': gi,

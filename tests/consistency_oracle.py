@@ -5,12 +5,12 @@ reference pins); everything after it is elementwise np.float32 arithmetic, one r
 Also here: the inputs the CPU and the GPU tier share (`case`), the categories a pixel can fall into (`categories`), and a stand-in for
 `_consistency.flow_consistency` for the host-logic tests (`fake_flow_consistency`)."""
 import functools
-import math
 
 import numpy as np
 import torch
 
 import oracle_backend as ob
+import special_values as sv
 
 ALPHA, BETA = 0.01, 0.5
 # (n, h, w): the frames of the GPU tier (tests/test_gpu_consistency.py says what each exercises)
@@ -51,7 +51,7 @@ def check(a, back, a_mask=None, back_mask=None, ref='s', alpha=ALPHA, beta=BETA)
     rec = np.zeros((n, 8), np.float64)
     for i in range(n):
         ek, ec = e[i][known[i]].astype(np.float64), e[i][consistent[i]].astype(np.float64)
-        rec[i, :5] = [ek.size, ec.size, math.fsum(ek), ek.max() if ek.size else 0.0, math.fsum(ec)]
+        rec[i, :5] = [ek.size, ec.size, sv.record_sum(ek), sv.record_max(ek), sv.record_sum(ec)]
     return {'du': du, 'dv': dv, 'known': known, 'error': error, 'consistent': consistent, 'records': rec}
 
 

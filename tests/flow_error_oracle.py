@@ -4,9 +4,9 @@ Per pixel, every step float32 with one rounding per operation: du = u - ug, dv =
 (np.sqrt on float32 is correctly rounded); a pixel counts where both masks are True (None: all True).  Counts are exact integers, sums are
 `math.fsum` of the float32 e: the correctly rounded float64 sum, whatever the order.  The gradient is computed per element in float64.
 """
-import math
-
 import numpy as np
+
+import special_values as sv
 
 RECORD = 16
 FL_ABS, FL_REL = np.float32(3.0), np.float32(0.05)
@@ -52,15 +52,15 @@ def score(est, gt, est_mask=None, gt_mask=None, thresholds=DEFAULT_THRESHOLDS):
     for i in range(n):
         ev, gv = e[i][valid[i]], g[i][valid[i]]
         out['count'][i] = ev.size
-        out['sum'][i] = math.fsum(ev.tolist())
-        out['max'][i] = float(ev.max()) if ev.size else 0.0
+        out['sum'][i] = sv.record_sum(ev)                                                # (total on NaN / inf terms: special_values.py)
+        out['max'][i] = sv.record_max(ev)
         for k, t in enumerate(thr):
             out['n_over'][i, k] = int(np.count_nonzero(ev > t))
         out['n_fl'][i] = int(np.count_nonzero((ev > FL_ABS) & (ev > FL_REL * gv)))       # the product in float32: no division at g = 0
         bins = [gv < SPEED_EDGES[0], (gv >= SPEED_EDGES[0]) & (gv < SPEED_EDGES[1]), ~(gv < SPEED_EDGES[1])]
         for b, sel in enumerate(bins):
             out['speed_count'][i, b] = int(np.count_nonzero(sel))
-            out['speed_sum'][i, b] = math.fsum(ev[sel].tolist())
+            out['speed_sum'][i, b] = sv.record_sum(ev[sel])
         r = out['records'][i]
         r[0], r[1], r[2], r[7] = out['count'][i], out['sum'][i], out['max'][i], out['n_fl'][i]
         r[3:3 + len(thr)] = out['n_over'][i]

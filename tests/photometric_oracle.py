@@ -8,7 +8,6 @@ inside tests of `grad_oracle64.warp_taps`; next to it `grad` returns, per elemen
 of the absolute contributions (they can cancel, so a bound on the gradient's error is relative to A, not to the gradient).
 """
 import functools
-import math
 
 import numpy as np
 import torch
@@ -16,6 +15,7 @@ import torch
 import consistency_oracle as co
 import grad_oracle64 as go
 import oracle_backend as ob
+import special_values as sv
 
 F32 = np.float32
 # (n, h, w): the smallest frame; one row / column pair; odd and smaller than a wave; 8 x 12 and up show every category
@@ -112,7 +112,7 @@ def compute(a, mask, img, other, ref, eps=0.001):
     rec = np.zeros((n, 8), np.float64)
     for i in range(n):
         vals = rho[i][known[i]].astype(np.float64)
-        rec[i, :3] = [vals.size, math.fsum(vals.tolist()), vals.max() if vals.size else 0.0]
+        rec[i, :3] = [vals.size, sv.record_sum(vals), sv.record_max(vals)]          # (total on NaN / inf terms: special_values.py)
     with np.errstate(invalid='ignore', divide='ignore'):
         loss = (rec[:, 1] / rec[:, 0]).astype(F32)
     return {'map': pmap, 'known': known, 'inside': inside, 'd': d, 'records': rec, 'photometric': loss}

@@ -7,9 +7,10 @@ A = |scale| * sum_k |coef_k q_Tk|, the sum of the absolute contributions (the co
 is relative to A, not to the gradient), and the pixels that a valid term reads.
 """
 import functools
-import math
 
 import numpy as np
+
+import special_values as sv
 
 F32 = np.float32
 TH, TW = 8, 128               # the kernel's tile (ofl_smoothness.hip)
@@ -135,8 +136,8 @@ def compute(flow, mask=None, img=None, order=1, alpha=10.0, eps=0.001):
     for i in range(n):
         vx, vy = tx['t'][i][tx['ok'][i]], ty['t'][i][ty['ok'][i]]
         rec[i, 0], rec[i, 1] = vx.size, vy.size
-        rec[i, 2], rec[i, 3] = math.fsum(vx.astype(np.float64).tolist()), math.fsum(vy.astype(np.float64).tolist())
-        rec[i, 4] = max([0.0] + ([float(vx.max())] if vx.size else []) + ([float(vy.max())] if vy.size else []))
+        rec[i, 2], rec[i, 3] = sv.record_sum(vx), sv.record_sum(vy)                     # (total on NaN / inf terms: special_values.py)
+        rec[i, 4] = sv.record_max(np.concatenate([vx, vy]))
     with np.errstate(invalid='ignore', divide='ignore'):
         loss = ((rec[:, 2] + rec[:, 3]) / (rec[:, 0] + rec[:, 1])).astype(F32)
     smap = tx['t'] + ty['t']

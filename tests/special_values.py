@@ -25,6 +25,8 @@ divided by the clamped density, then the un-occlude fill.  A PREDICATE decides w
 
 On finite data every predicate gives the reference's bits: all a predicate removes is the addition of a zero.
 """
+import math
+
 import numpy as np
 
 F32 = np.float32
@@ -63,6 +65,25 @@ def same_bits(got, exp):
         return got == exp
     u = {4: np.uint32, 2: np.uint16}[got.dtype.itemsize]
     return np.where(np.isnan(exp), np.isnan(got), got.view(u) == exp.view(u))
+
+
+def record_sum(terms):
+    """The sum of a record over terms that are not negative: NaN if a term is NaN, else +inf if a term is +inf, else math.fsum (the
+    exact sum rounded once)."""
+    terms = np.asarray(terms, np.float64).reshape(-1)
+    if np.isnan(terms).any():
+        return float("nan")
+    if np.isposinf(terms).any():
+        return float("inf")
+    return math.fsum(terms.tolist())
+
+
+def record_max(terms):
+    """The maximum of a record: the largest term that is not NaN (+inf included), 0 if there is none -- the selection `t > mx` from
+    mx = 0, which a NaN never passes."""
+    terms = np.asarray(terms, np.float64).reshape(-1)
+    terms = terms[~np.isnan(terms)]
+    return float(terms.max()) if terms.size else 0.0
 
 
 def describe(got, exp, limit=6):
@@ -340,18 +361,22 @@ def _plant_cycle(i, half):
     return pool[i % len(pool)]
 
 
-def warp_case(n, h, w, c, seed=0, half=False, sprinkle=0.02):
+def warp_case(n, h, w, c, seed=0, half=False, sprinkle=0.02, finite=False, plant_names=None):
     """A backward-warp input with specials in the source.  The output pixel (x, y) samples the source at (x - u, y - v).
     -> dict(flow [n,2,h,w], src [n,c,h,w], names {name: [(y, x)]} the OUTPUT pixels (the same in every image) whose sample position is
     the named one, weight0 [(y, x)] the SOURCE pixels that hold a special and are read by a named output pixel only through a tap of
-    weight 0).  The source also carries specials on a random `sprinkle` of its pixels, another draw for each image."""
+    weight 0, aimed {name: (sy, sx)} the integer position each name aims at, planted [(y, x)] every SOURCE pixel a name planted a
+    special on).  The source also carries specials on a random `sprinkle` of its pixels, another draw for each image.  finite: the
+    same flow and the same finite source values, no special anywhere (the lists say where they would be); plant_names: the names
+    whose source pixel receives a special (default: all of them)."""
     rng = np.random.default_rng(77 * seed + 13 * h + w + 1000 * c)
     flow = (rng.integers(-320, 320, size=(n, 2, h, w)) / 64.0).astype(np.float32)
     src = (rng.integers(0, 2048, size=(n, c, h, w)) / (128.0 if half else 8.0)).astype(np.float32)      # (11 bits: exact in fp16)
     hit = rng.random((n, c, h, w)) < sprinkle
     pool = np.array([_plant_cycle(i, half) for i in range(7)], np.float32)
-    src[hit] = pool[np.arange(int(hit.sum())) % len(pool)]
-    names, weight0 = {}, []
+    if not finite:
+        src[hit] = pool[np.arange(int(hit.sum())) % len(pool)]
+    names, weight0, aimed, planted = {}, [], {}, []
     outs = [(y, x) for y in range(0, h) for x in range(0, w)]
     outs = [outs[i] for i in rng.permutation(len(outs))]
 
@@ -360,12 +385,15 @@ def warp_case(n, h, w, c, seed=0, half=False, sprinkle=0.02):
         y, x = outs.pop()
         flow[:, 0, y, x], flow[:, 1, y, x] = x - sx, y - sy
         py, px = (sy, sx) if plant is None else plant
-        if 0 <= py < h and 0 <= px < w:
-            for ch in range(c):
-                src[:, ch, py, px] = NONFINITE[(special_i + ch) % 3]
+        if 0 <= py < h and 0 <= px < w and (plant_names is None or name in plant_names):
+            if not finite:
+                for ch in range(c):
+                    src[:, ch, py, px] = NONFINITE[(special_i + ch) % 3]
+            planted.append((py, px))
             if plant is not None:
                 weight0.append((py, px))
         names.setdefault(name, []).append((y, x))
+        aimed[name] = (sy, sx)
 
     ey, ex = exact_coords(h), exact_coords(w)
     my, mx = _nearest(ey, h // 2), _nearest(ex, w // 2)
@@ -390,7 +418,7 @@ def warp_case(n, h, w, c, seed=0, half=False, sprinkle=0.02):
         y, x = outs.pop()
         flow[:, i % 2, y, x] = e
         names.setdefault("flow_extreme", []).append((y, x))
-    return dict(flow=flow, src=src, names=names, weight0=weight0, n=n, h=h, w=w, c=c, half=half)
+    return dict(flow=flow, src=src, names=names, weight0=weight0, aimed=aimed, planted=planted, n=n, h=h, w=w, c=c, half=half)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
