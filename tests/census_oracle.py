@@ -32,6 +32,7 @@ UPSTREAM = po.UPSTREAM
 REFS = po.REFS
 sign_of = po.sign_of
 ulp32 = po.ulp32
+grad_bound = po.grad_bound
 
 
 # ---- the definition -------------------------------------------------------------------------------------------------------------------

@@ -15,7 +15,11 @@ REACH.  The launcher's thresholds count 32 x 16 tiles (g1) and 32 x 64 groups (g
 (ofl_kernels.hip) -- pinned on the CPU against every recorded case of tests/golden/warp_kernel_choice.json by
 tests/test_frame_sweep_host.py, and on the GPU by the name of every swept launch.  `batch_for(case, h, w)` tries the batches on
 either side of each threshold in that frame's g1 and g4 (rounded as `_sides()` of tests/test_gpu_warp_kernel_choice.py) and keeps the
-smallest whose choice is the base case's; None where no batch can (H <= 16: g1 == g4, so g1 >= kColumnMinGroups > g4 never holds)."""
+smallest whose choice is the base case's; None where no batch can (H <= 16: g1 == g4, so g1 >= kColumnMinGroups > g4 never holds).
+
+THE LOSS SWEEP (the last part of this file): the fused loss kernels and the backward of the scores on the same frames and content --
+their geometry read from the sources, the operands, the frames that reach each state of each block loop, the kernels' index walks
+restated, and the rule that spreads the variants over the frames."""
 import json
 import os
 import re
@@ -322,3 +326,258 @@ def residue_gaps(case, frames):
 def load_table():
     with open(os.path.join(ROOT, 'tests', 'golden', 'warp_kernel_choice.json')) as fh:
         return json.load(fh)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# the loss sweep: the fused loss kernels and the backward of the scores
+# ------------------------------------------------------------------------------------------------------------------------------------
+# ofl_smoothness.hip, ofl_photometric.hip, ofl_census.hip and flow_epe_grad_kernel of ofl_metrics.hip.  Every number below comes from
+# `loss_geometry()`, which reads the constants out of the sources; tests/test_loss_sweep_host.py holds it to a literal table and proves,
+# through a restatement of each kernel's index walk, that every frame of LOOP_FRAMES reaches the loop state it is listed for.
+def _source(name):
+    with open(os.path.join(ROOT, 'oflibpytorch_amd', 'csrc', name)) as fh:
+        return fh.read()
+
+
+def _constant(text, name):
+    """`name = <number>` of a constexpr line (one line may define several: `constexpr int kTH = 8, kTW = 128;`)"""
+    m = re.search(r"constexpr int [^;\n]*\b%s = (\d+)[,;]" % name, text)
+    assert m, name
+    return int(m.group(1))
+
+
+_GEOMETRY = None
+
+
+def loss_geometry():
+    """{family: {constant: value}} read from the four sources; for the metrics also `grad_pixels`, the pixels one thread of
+    flow_epe_grad_kernel takes per step (from the shift that forms its number of quads)."""
+    global _GEOMETRY
+    if _GEOMETRY is None:
+        names = {"smoothness": ("kTH", "kTW", "kMaxBlocks", "kMaxGradBlocks"), "census": ("kTileW", "kTileH", "kChunk"),
+                 "photometric": ("kThreads", "kMaxBlocks", "kMaxGradBlocks"), "metrics": ("kThreads", "kMaxBlocks", "kMaxGradBlocks")}
+        out = {fam: {k: _constant(_source("ofl_%s.hip" % fam), k) for k in ks} for fam, ks in names.items()}
+        body = re.search(r"flow_epe_grad_kernel\(ErrParams p\) \{(.*?)\n\}", _source("ofl_metrics.hip"), re.S).group(1)
+        add, shift = map(int, re.search(r"quads = \(p\.hw \+ (\d+)\) >> (\d+)", body).groups())
+        assert add == (1 << shift) - 1
+        out["metrics"]["grad_pixels"] = 1 << shift
+        _GEOMETRY = out
+    return _GEOMETRY
+
+
+LOSS_UPSTREAM = (0.75, -2.0, 1.0, 0.5)        # one upstream gradient per image of a frame (the oracles' own UPSTREAM has three)
+_LOSS_INPUTS = {}
+
+
+def loss_inputs(h, w):
+    """The operands of the loss kernels from `content(h, w)`, the same arrays on every call (read-only): `flow` [4,2,h,w] fp32 and
+    `flow16` as stored fp16, `mask` = m1, `img` = src[:, 0:3] / 255 (fp32; `img_u8` the same samples as uint8), `other` = src[:, 3:6] / 255
+    (`other_u8`).  One channel: plane 0 alone (`images()`).  The smoothness guidance image is `img`.  A frame of one row or one column
+    (smoothness alone takes those; `content()` needs H, W >= 2) is cut from the content of the frame with 2 in that axis."""
+    if (h, w) not in _LOSS_INPUTS:
+        t = content(max(h, 2), max(w, 2))
+        cut = lambda a: np.ascontiguousarray(a[..., :h, :w])
+        src = cut(t["src"])
+        out = dict(flow=cut(t["flow"]), mask=cut(t["m1"]), img=src[:, 0:3] / F32(255), other=src[:, 3:6] / F32(255),
+                   img_u8=src[:, 0:3].astype(np.uint8), other_u8=src[:, 3:6].astype(np.uint8))
+        with np.errstate(over='ignore'):                                   # (a named pixel of a frame wider than 65 504 samples further
+            out["flow16"] = out["flow"].astype(np.float16)                 # away than fp16 holds: inf, and the pixel is not known)
+        assert out["img"].dtype == F32 and np.array_equal(out["img_u8"].astype(F32), src[:, 0:3])
+        for a in out.values():
+            a.setflags(write=False)
+        _LOSS_INPUTS[(h, w)] = out
+        if h * w > 1 << 16:                                                # a loop frame: its content is not kept twice
+            _CONTENT.pop((max(h, 2), max(w, 2)), None)
+    return _LOSS_INPUTS[(h, w)]
+
+
+def images(t, u8, chan, images=None):
+    """(img, other) of `loss_inputs` as uint8 or fp32, with 3 channels or plane 0 alone; `images`: those of the batch alone."""
+    pair = (t["img_u8"], t["other_u8"]) if u8 else (t["img"], t["other"])
+    sel = slice(None) if images is None else list(images)
+    return tuple(np.ascontiguousarray(a[sel, :chan]) for a in pair)
+
+
+# ---- the frames ----------------------------------------------------------------------------------------------------------------------
+WIDE_LINE = [(17, w) for w in range(252, 262)]          # a 128-wide tile with a neighbour on both sides (and the 64-wide one: 4 or 5 across)
+LOSS_TILE_FRAMES = sorted(set(FRAMES + WIDE_LINE))
+SMOOTHNESS_ONLY = [(1, 5), (5, 1), (1, 1)]             # the other families refuse H or W < 2
+
+
+def stream_sizes(*es):
+    """The frames of the streaming sweep (tests/test_gpu_frame_sweep_stream.py) for one block step E or several: every h w from 4 to
+    max E + 8 that a 2 x k or 3 x k frame has, and k E - 3 ... k E + 5 for k = 2, 3 and each E."""
+    import test_gpu_frame_sweep_stream as st
+    return st._sizes_of(list(es))
+
+
+def photo_sizes():
+    return stream_sizes(loss_geometry()["photometric"]["kThreads"])
+
+
+def _isqrt(v):
+    r = int(np.sqrt(v))
+    while r * r > v:
+        r -= 1
+    while (r + 1) * (r + 1) <= v:
+        r += 1
+    return r
+
+
+def loop_frames():
+    """{kernel: [(state, h, w)]}: per kernel the smallest frames that reach each state of its block loop, from `loss_geometry()`.
+    tests/test_loss_sweep_host.py asserts each state through the walks below."""
+    g = loss_geometry()
+    out = {}
+    for name, cap in (("photometric_fwd", "kMaxBlocks"), ("photometric_bwd", "kMaxGradBlocks")):
+        t = g["photometric"]["kThreads"]
+        s = g["photometric"][cap] * t                                       # pixels of one round of the whole grid
+        r = _isqrt(s) + 1
+        frames = [("partial_second_round", r, r), ("step_x_zero", s // (2 * t) + 1, 2 * t), ("second_row", 2, s // 2 + 3),
+                  ("step_y_zero", 2, s + 3)]
+        if name == "photometric_fwd":
+            frames += [("step_x_zero", s // t + 2, t), ("three_rounds", 3, 2 * s // 3 + 10)]
+        out[name] = frames
+    th, tw = g["smoothness"]["kTH"], g["smoothness"]["kTW"]
+    for name, cap in (("smoothness_fwd", g["smoothness"]["kMaxBlocks"]), ("smoothness_bwd", g["smoothness"]["kMaxGradBlocks"])):
+        rows = cap // 2 + 2                                                 # tile rows of a frame two tiles wide: four tiles over the cap,
+                                                                            # a row of them inside the frame and the ragged last row
+        out[name] = [("ragged_scalar", th * (rows - 1) + 1, tw + 1), ("ragged_vector", th * (rows - 1) + 1, tw + 4),
+                     # three rounds, three tiles across (the middle one re-staged with a neighbour's pixels on both sides)
+                     ("three_rounds", th * (-(-(2 * cap + 1) // 3) - 1) + 1, 2 * tw + 4)]
+    cw, ch, chunk = g["census"]["kTileW"], g["census"]["kTileH"], g["census"]["kChunk"]
+    # (a last tile row of ch / 2 + 1 rows, not of one: on a single last row the content's flow leaves the frame all along the stretch
+    # of a few tiles, and the records of the last chunk would all be zero -- tests/test_loss_sweep_host.py asserts that they are not)
+    out["census_finish"] = [("one_full_chunk", 2 * ch, cw * chunk // 2), ("full_chunk_and_two", ch + ch // 2 + 1, cw * chunk // 2 + 1),
+                            ("two_full_chunks", 2 * ch, cw * chunk), ("three_chunks", 2 * ch + ch // 2 + 1, cw * (2 * chunk // 3) + 1)]
+    e = g["metrics"]["kThreads"] * g["metrics"]["grad_pixels"]
+    out["epe_grad"] = [("second_round", 2, g["metrics"]["kMaxGradBlocks"] * e // 2 + 3)]
+    return out
+
+
+def census_chunk_variant(h, w, patch):
+    """The variant a chunk frame runs at `patch`: the frame's own (HALF, U8) number patch % 4, with q = 1 (the map bit for bit)"""
+    return dict(photometric_variants(h, w)[patch % 4], patch=patch, q1=True)
+
+
+# ---- the walks: each kernel's index arithmetic restated ------------------------------------------------------------------------------
+def photometric_walk(h, w, backward):
+    """flow_photometric_kernel's walk over an image, every lane of the grid at once: dict(rounds, step_x, step_y, wraps, straight,
+    exact, first_round_wrap) -- the carried (x, y) is asserted equal to divmod(pix, w) at every pixel of every round; `wraps` /
+    `straight` count the two branches of `if (x >= w)` over the carries whose round exists, `exact` those with x + step_x == w."""
+    g = loss_geometry()["photometric"]
+    t, cap = g["kThreads"], g["kMaxGradBlocks" if backward else "kMaxBlocks"]
+    hw = h * w
+    stride = min(-(-hw // t), cap) * t
+    step_y, step_x = divmod(stride, w)
+    pix = np.arange(stride, dtype=np.int64)
+    y, x = np.divmod(pix, w)
+    seen = np.zeros(hw, np.int32)
+    out = dict(rounds=0, step_x=step_x, step_y=step_y, wraps=0, straight=0, exact=0, first_round_wrap=False)
+    while True:
+        live = pix < hw
+        if not live.any():
+            break
+        assert np.array_equal(y[live] * w + x[live], pix[live]) and (x[live] < w).all() and (y[live] < h).all(), (h, w, out["rounds"])
+        np.add.at(seen, pix[live], 1)
+        nxt = pix + stride < hw
+        x, y = x + step_x, y + step_y
+        wrap = x >= w
+        if nxt.any():
+            out["wraps"] += int((wrap & nxt).sum())
+            out["straight"] += int((~wrap & nxt).sum())
+            out["exact"] += int(((x == w) & nxt).sum())
+            out["first_round_wrap"] |= out["rounds"] == 0 and bool((wrap & nxt).any())
+        x, y = np.where(wrap, x - w, x), np.where(wrap, y + 1, y)
+        pix = pix + stride
+        out["rounds"] += 1
+    assert (seen == 1).all(), (h, w)
+    return out
+
+
+def smoothness_walk(h, w, backward):
+    """flow_smoothness_kernel's walk: dict(tiles, tiles_x, tiles_y, nblk, rounds (of the busiest block), vec, later: the set of
+    (ragged row, ragged column, neighbours on both sides in x, in y) of the tiles a block takes AFTER its first)."""
+    g = loss_geometry()["smoothness"]
+    th, tw, cap = g["kTH"], g["kTW"], g["kMaxGradBlocks" if backward else "kMaxBlocks"]
+    tiles_x, tiles_y = -(-w // tw), -(-h // th)
+    tiles = tiles_x * tiles_y
+    nblk = min(tiles, cap)
+    later, taken = set(), np.zeros(tiles, np.int32)
+    for b in range(nblk):
+        for k, tile in enumerate(range(b, tiles, nblk)):
+            taken[tile] += 1
+            ty, tx = divmod(tile, tiles_x)
+            if k > 0:
+                later.add((ty == tiles_y - 1 and h % th != 0, tx == tiles_x - 1 and w % tw != 0, 0 < tx < tiles_x - 1, 0 < ty < tiles_y - 1))
+    assert (taken == 1).all()
+    return dict(tiles=tiles, tiles_x=tiles_x, tiles_y=tiles_y, nblk=nblk, rounds=-(-tiles // nblk), vec=w % 4 == 0, later=later)
+
+
+def census_walk(h, w):
+    """flow_census_finish_kernel's chunks: dict(nblk, tiles_x, tiles_y, chunks [(base, cnt)])."""
+    g = loss_geometry()["census"]
+    tiles_x, tiles_y = -(-w // g["kTileW"]), -(-h // g["kTileH"])
+    nblk = tiles_x * tiles_y
+    chunks = [(base, min(nblk - base, g["kChunk"])) for base in range(0, nblk, g["kChunk"])]
+    assert sum(c for _, c in chunks) == nblk
+    return dict(nblk=nblk, tiles_x=tiles_x, tiles_y=tiles_y, chunks=chunks)
+
+
+def census_block_counts(known):
+    """The count field of flow_census_kernel's block records from the oracle's `known` [n,h,w]: [n, nblk], blocks in the kernel's order"""
+    g = loss_geometry()["census"]
+    n, h, w = known.shape
+    ty, tx = -(-h // g["kTileH"]), -(-w // g["kTileW"])
+    pad = np.zeros((n, ty * g["kTileH"], tx * g["kTileW"]), np.int64)
+    pad[:, :h, :w] = known
+    return pad.reshape(n, ty, g["kTileH"], tx, g["kTileW"]).sum((2, 4)).reshape(n, ty * tx)
+
+
+def epe_grad_walk(h, w):
+    """flow_epe_grad_kernel's walk over quads: dict(quads, stride, rounds, last: quads of the last round)."""
+    g = loss_geometry()["metrics"]
+    quads = -(-h * w // g["grad_pixels"])
+    stride = min(-(-quads // g["kThreads"]), g["kMaxGradBlocks"]) * g["kThreads"]
+    rounds = -(-quads // stride)
+    return dict(quads=quads, stride=stride, rounds=rounds, last=quads - (rounds - 1) * stride)
+
+
+# ---- the variants of a frame: a fixed rule keyed on the frame -------------------------------------------------------------------------
+# Every frame runs every (HALF, U8) instantiation of the photometric kernel and every (ORDER, IMG) one of the smoothness kernel, so each
+# meets every residue the frames have.  What is no template argument (the ref, the channels, the mask, fp16 storage for smoothness) is
+# spread by the frame's key, another value for the next instantiation.  The census kernels are (PATCH, HALF, U8): a frame runs every
+# (HALF, U8) at one patch each -- (h + w + j) % 3, so that neighbouring widths and heights give an instantiation its three residues --
+# and at all three where the frame is no larger than the backward's halo of the widest patch in either axis.
+CENSUS_PATCHES = (3, 5, 7)
+TYPES = [(False, False), (False, True), (True, False), (True, True)]        # (fp16 vectors, uint8 images)
+
+
+def frame_key(h, w):
+    return 5 * h + w
+
+
+def photometric_variants(h, w):
+    """[dict(half, u8, ref, chan, masked)], one per (HALF, U8)."""
+    k = frame_key(h, w)
+    return [dict(half=hf, u8=u8, ref='st'[(k + j) % 2], chan=(3, 1)[(k // 2 + j) % 2], masked=(k // 4 + j) % 2 == 0)
+            for j, (hf, u8) in enumerate(TYPES)]
+
+
+def census_variants(h, w):
+    """[dict(patch, half, u8, ref, chan, masked, q1)]: `q1`: q = 1 (the map bit for bit), else the default q."""
+    out = []
+    for j, v in enumerate(photometric_variants(h, w)):
+        small = min(h, w) <= 2 * (max(CENSUS_PATCHES) // 2)
+        for p in (CENSUS_PATCHES if small else (CENSUS_PATCHES[(h + w + j) % 3],)):
+            out.append(dict(v, patch=p, q1=(frame_key(h, w) // 8 + j + p // 2) % 2 == 0))
+    return out
+
+
+SMOOTHNESS_KINDS = [(o, i) for o in (1, 2) for i in (None, "f32", "u8")]     # (ORDER, IMG)
+
+
+def smoothness_variants(h, w):
+    """[dict(order, kind, half, masked)], one per (ORDER, IMG)."""
+    k = frame_key(h, w)
+    return [dict(order=o, kind=i, half=(k + j) % 2 == 1, masked=(k // 2 + j) % 2 == 0) for j, (o, i) in enumerate(SMOOTHNESS_KINDS)]

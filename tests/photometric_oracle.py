@@ -160,6 +160,11 @@ def ulp32(x):
     return 2.0 ** (np.floor(np.log2(x)) - 23)
 
 
+def grad_bound(want, big_a):
+    """The gradient's bar per element: 2^-22 of the sum of the absolute contributions plus one float32 step of the value"""
+    return 2.0 ** -22 * big_a + ulp32(want)
+
+
 def categories(n, h, w, ref):
     """Per image of a case, the share of its pixels that are known, unknown because the sample leaves the frame, unknown by the mask
     alone: three float arrays [n]"""

@@ -196,6 +196,11 @@ def ulp32(x):
     return 2.0 ** (np.floor(np.log2(x)) - 23)
 
 
+def grad_bound(want, big_a):
+    """The gradient's bar per element: 2^-22 of the sum of the absolute contributions plus one float32 step of the value"""
+    return 2.0 ** -22 * big_a + ulp32(want)
+
+
 # ---- the native call served by this module (host-logic tests) -----------------------------------------------------------------------
 def fake_flow_smoothness(vecs, mask=None, img=None, order=1, alpha=10.0, eps=0.001, want_map=False):
     import torch

@@ -20,6 +20,7 @@ SMALL = [(3, 2, 2), (3, 5, 7), (3, 37, 53), (3, 96, 136)]
 LARGE = (2, 1080, 1920)
 FRAMES = SMALL + [LARGE]
 THRESHOLDS = (1, 3, 5)
+GRAD_ULPS = 4.0               # the gradient's bar: float32 ulp of each element's own magnitude
 # the tie pixels of the CPU tier: ground truth vectors and the error added to them (e exactly 1, 3, 5, 0, 10, 5; g exactly 0, 10, 40, 5, 50, 100)
 TIE_GT = np.array([[0, 0], [6, 8], [24, 32], [3, 4], [30, 40], [60, 80]], np.float32)
 TIE_D = np.array([[1, 0], [0, 3], [3, 4], [0, 0], [6, 8], [3, 4]], np.float32)
@@ -206,7 +207,7 @@ def _ulp_check(got, want):
     ulp = np.spacing(np.abs(want).astype(np.float32)).astype(np.float64)
     worst = float(np.max(np.abs(got64 - want) / ulp))
     print("worst gradient error: %.3f ulp" % worst)
-    assert worst <= 4.0
+    assert worst <= GRAD_ULPS
     assert not got[want == 0].any()
 
 

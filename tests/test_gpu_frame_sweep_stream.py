@@ -6,7 +6,7 @@ block covers in one step, E, differs (STEP below: pixels per thread and step of 
   flow_f16_kernel       4 pixels x 4 groups = 16 a thread, E = 4096 (h w % 4 == 0 only: other sizes are converted and take flow_flags_kernel)
   warp_valid_kernel     VEC (w % 4 == 0): 4 a thread, E = 1024; scalar: E = 256
   flow_extents_kernel   1 a thread, E = 256
-  flow_error_kernel, flow_consistency_kernel   quads with a guarded last one: 4 a thread, E = 1024
+  flow_error_kernel, flow_consistency_kernel, flow_epe_grad_kernel   quads with a guarded last one: 4 a thread, E = 1024
 Swept per kernel: every h * w from 4 to E + 8 (E of its larger form) that a frame 2 x k or 3 x k has, and k * E - 3 ... k * E + 5 for
 k = 2, 3 and each of its forms' E.  H >= 2 and W >= 2 throughout.
 
@@ -19,7 +19,10 @@ k = 2, 3 and each of its forms' E.  H >= 2 and W >= 2 throughout.
   flow_extents                               oracle.flow_extents
   flow_error                                 tests/flow_error_oracle.py: the map bit for bit, the counts and the maximum exactly, the
                                              float64 sums within count * 2^-52 relative (the bar of tests/test_gpu_flow_error.py)
-  flow_consistency                           tests/consistency_oracle.py: maps bit for bit, counts and maximum exactly, sums as above"""
+  flow_consistency                           tests/consistency_oracle.py: maps bit for bit, counts and maximum exactly, sums as above
+  flow_epe_grad                              flow_error_oracle.epe_grad in float64: both gradients within 4 float32 ulp (the bar of
+                                             tests/test_gpu_flow_error.py), exactly 0 where the oracle is, grad_gt the negation bit for
+                                             bit; the same on the one frame whose quads exceed the backward's largest grid (its loop)"""
 import os
 import re
 
@@ -29,6 +32,7 @@ import torch
 
 import consistency_oracle as co
 import flow_error_oracle as feo
+import frame_sweep as fs
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,7 +51,8 @@ def _threads(source, kernel):
 # kernel -> (source, pixels per thread and block step of each of its forms, the larger first)
 STEP = {"flow_flags_kernel": ("ofl_kernels.hip", (16, 1)), "flow_f16_kernel": ("ofl_kernels.hip", (16,)),
         "warp_valid_kernel": ("ofl_aux_kernels.hip", (4, 1)), "flow_extents_kernel": ("ofl_aux_kernels.hip", (1,)),
-        "flow_error_kernel": ("ofl_metrics.hip", (4,)), "flow_consistency_kernel": ("ofl_consistency.hip", (4,))}
+        "flow_error_kernel": ("ofl_metrics.hip", (4,)), "flow_consistency_kernel": ("ofl_consistency.hip", (4,)),
+        "flow_epe_grad_kernel": ("ofl_metrics.hip", (4,))}
 
 
 def _steps(kernel):
@@ -65,16 +70,20 @@ def _frame_of(hw):
     return (3, hw // 3) if hw % 3 == 0 and hw >= 6 else None
 
 
-def _sizes(*kernels):
-    """The frames of the sweep for kernels that share a test (the union of their ranges)."""
+def _sizes_of(*forms):
+    """The frames of the sweep for the block steps of one kernel's forms, or of several kernels' (the union of their ranges)."""
     vals = set()
-    for kernel in kernels:
-        es = _steps(kernel)
+    for es in forms:
         vals.update(range(4, max(es) + 9))
         for e in es:
             for k in (2, 3):
                 vals.update(range(k * e - 3, k * e + 6))
     return [f for f in map(_frame_of, sorted(vals)) if f is not None]
+
+
+def _sizes(*kernels):
+    """The frames of the sweep for kernels that share a test."""
+    return _sizes_of(*(_steps(kernel) for kernel in kernels))
 
 
 @pytest.fixture(scope="module")
@@ -87,7 +96,9 @@ def dev():
 
 def test_the_sweep_covers_one_block_step_of_every_kernel():
     assert {k: _steps(k) for k in STEP} == {"flow_flags_kernel": [4096, 256], "flow_f16_kernel": [4096], "warp_valid_kernel": [1024, 256],
-                                            "flow_extents_kernel": [256], "flow_error_kernel": [1024], "flow_consistency_kernel": [1024]}
+                                            "flow_extents_kernel": [256], "flow_error_kernel": [1024], "flow_consistency_kernel": [1024],
+                                            "flow_epe_grad_kernel": [1024]}
+    assert STEP["flow_epe_grad_kernel"][1] == (fs.loss_geometry()["metrics"]["grad_pixels"],)
     for kernel in STEP:
         sizes = _sizes(kernel)
         hw = {h * w for h, w in sizes}
@@ -224,6 +235,51 @@ def test_flow_error_at_every_size(dev):
             _sums_within(rec[i, 1], ref['sum'][i], ref['count'][i], where)
             for b in range(3):
                 _sums_within(rec[i, 11 + b], ref['speed_sum'][i, b], ref['speed_count'][i, b], where)
+
+
+def _epe_grad_frame(tfe, dev, n, h, w, est, gt, em, gm):
+    """One launch of flow_epe_grad_kernel against the float64 oracle; returns the worst error in ulp."""
+    from oflibpytorch_amd import _native
+    where = "%d x %d (h w = %d)" % (h, w, h * w)
+    count = feo.valid_of((n, h, w), em, gm).reshape(n, -1).sum(1)
+    assert (count > 0).all(), where
+    scale = (np.array([0.75, -2.0, 1.0], np.float32)[:n].astype(np.float64) / count).astype(np.float32)
+    want = feo.epe_grad(est, gt, em, gm, scale)
+    g_est, g_gt = _native.flow_epe_grad(*(torch.from_numpy(a).to(dev) for a in (est, gt, em, gm)), torch.from_numpy(scale).to(dev), True, True)
+    assert 'flow_epe_grad_kernel' in _native.last_kernel_name()
+    assert torch.equal(g_gt.view(torch.int32), (-g_est).view(torch.int32)), where
+    got = g_est.cpu().numpy()
+    assert got.shape == want.shape and got.dtype == np.float32
+    ulp = np.spacing(np.abs(want).astype(np.float32)).astype(np.float64)
+    err = np.abs(got.astype(np.float64) - want) / ulp
+    bad = np.argwhere((err > tfe.GRAD_ULPS) | ((want == 0) & (got != 0)))      # (a zero of either sign: scale * 0 / e)
+    assert not len(bad), "%s: the gradient differs first at (n, c, y, x) %s: got %r, expected %r" % (
+        where, bad[0].tolist(), got[tuple(bad[0])], want[tuple(bad[0])])
+    return float(err.max()), bool((want == 0).any() and (want != 0).any()), want
+
+
+def test_flow_epe_grad_at_every_size(dev):
+    import test_gpu_flow_error as tfe
+    n, worst, mixed = 2, 0.0, 0
+    sizes = _sizes("flow_epe_grad_kernel")
+    for h, w in sizes:
+        e, m, _ = _epe_grad_frame(tfe, dev, n, h, w, *tfe._case.__wrapped__(n, h, w))
+        worst, mixed = max(worst, e), mixed + m
+    assert mixed == len(sizes)                                             # zeros (a hole, the tie with e = 0) and non-zeros side by side
+    print("flow_epe_grad: worst %.3f ulp over %d sizes" % (worst, len(sizes)))
+
+
+def test_flow_epe_grad_where_the_grid_loops(dev):
+    """The one frame just over kMaxGradBlocks blocks of quads: the second round of the grid-stride loop (its last quad a partial one),
+    which tests/test_loss_sweep_host.py proves from the constants."""
+    import test_gpu_flow_error as tfe
+    (state, h, w), = fs.loop_frames()["epe_grad"]
+    walk = fs.epe_grad_walk(h, w)
+    assert walk["rounds"] == 2 and 0 < walk["last"] < walk["stride"] and (h * w) % 4 != 0
+    est, gt, em, gm = tfe._case.__wrapped__(1, h, w)
+    e, m, want = _epe_grad_frame(tfe, dev, 1, h, w, est, gt, em, gm)
+    assert m and (want.reshape(1, 2, -1)[:, :, 4 * walk["stride"]:] != 0).any()             # (the second round has a gradient to get wrong)
+    print("flow_epe_grad, %d x %d: worst %.3f ulp" % (h, w, e))
 
 
 @pytest.mark.parametrize("ref", ["s", "t"])

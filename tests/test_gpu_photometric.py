@@ -150,7 +150,7 @@ def test_gradient_against_the_float64_oracle(n, h, w):
             assert not got[unknown].view(np.uint32).any(), what                               # exactly +0 where not known
             assert np.isfinite(got).all(), what
             assert h * w < 35 or (want != 0).any(), what                                      # the oracle's gradient is not vacuous
-            bound = 2.0 ** -22 * big_a + po.ulp32(want)
+            bound = po.grad_bound(want, big_a)
             err = np.abs(got.astype(np.float64) - want)
             worst = max(worst, float((err / bound).max()))
             assert np.all(err <= bound), (what, float((err / bound).max()))

@@ -21,6 +21,7 @@ LARGE = so.FRAMES[-1]
 ORDERS = (1, 2)
 IMAGES = {"f32c3": dict(c=3), "u8c3": dict(c=3, u8=True), "f32c1": dict(c=1), "chw": dict(c=3, batch=False)}
 ALPHA = 10.0
+MAP_ULPS, MAX_ULPS = 4, 2     # with an image: the bars of a map element and of the record's maximum, float32 ulp
 
 
 def _dev():
@@ -152,7 +153,7 @@ def test_with_an_image_the_map_is_within_4_ulp(n, h, w):
         if bearing.any():
             d = _ulps(got[bearing], ref['map'][bearing])
             worst_map = max(worst_map, int(d.max()))
-            assert d.max() <= 4, (what, int(d.max()))
+            assert d.max() <= MAP_ULPS, (what, int(d.max()))
         _, rec = _record(flow, img, order, 1e-3)
         want = ref['records']
         assert np.array_equal(rec[:, :2], want[:, :2]), what
@@ -164,7 +165,7 @@ def test_with_an_image_the_map_is_within_4_ulp(n, h, w):
         dm = _ulps(rec[:, 4].astype(np.float32), want[:, 4].astype(np.float32))
         assert np.array_equal(rec[:, 4].astype(np.float32).astype(np.float64), rec[:, 4])    # a float32 value
         worst_max = max(worst_max, int(dm.max()))
-        assert dm.max() <= 2, what
+        assert dm.max() <= MAX_ULPS, what
     print("%d x %d: largest map error %d ulp (bar 4), sum error %.3g of its bound, max error %d ulp (bar 2)" % (h, w, worst_map, worst_sum,
                                                                                                               worst_max))
 
@@ -253,7 +254,7 @@ def test_gradient_against_the_float64_oracle(n, h, w):
             if h * w == 1:
                 assert not got.view(np.uint32).any() and bool(torch.isnan(loss).all())
             assert h * w < 35 or (want != 0).any(), what                                      # the oracle's gradient is not vacuous
-            bound = 2.0 ** -22 * a + so.ulp32(want)
+            bound = so.grad_bound(want, a)
             err = np.abs(got.astype(np.float64) - want.astype(np.float64))
             worst = max(worst, float((err / bound).max()))
             assert np.all(err <= bound), (what, float((err / bound).max()))
