@@ -1042,6 +1042,59 @@ int ofl_flow_census_grad_f32(const void* flow, int64_t flow_bs, int32_t flow_hal
                              int32_t patch, float thresh, float eps, float q, const float* scale, float* grad, int32_t n, int32_t h,
                              int32_t w, void* stream);
 
+/*
+ * The structural-similarity data term of an unsupervised flow loss, warp and windowed comparison in one pass (which
+ * defines the numbers; ofl_ssim.hip): Flow.ssim / ssim_map / ssim_stats.  An extension: the reference has no such function.  `img`,
+ * `other`, flow_sign and the reading of a uint8 sample (float(s) / 255.0f) as for ofl_flow_photometric_f64, C = 1 or 3.  window is 3, 5
+ * or 7, R = window / 2.  Every step fp32 with one rounding per operation unless it says float64:
+ *   X_c = Iw_c, mr  as in ofl_flow_photometric_f64;  Y_c = img_c
+ *   usable(p)   p in the frame, valid in the mask, mr(p) > 0.99999f; a pixel that is not usable loads no image sample
+ *   W(p)        the usable pixels p + o with |dy|, |dx| <= R, the centre included; n(p) their number; known(p) = usable(p)
+ *   per channel, two walks of W(p), dy ascending, dx ascending within it:
+ *     mux = (sum X) / float(n), muy likewise;  sxx = (sum (X - mux) (X - mux)) / float(n), syy and sxy likewise (each product rounded,
+ *     then added)
+ *     l1 = (2 mux) muy + c1   l2 = (mux mux + muy muy) + c1   s1 = 2 sxy + c2   s2 = (sxx + syy) + c2
+ *     d_c = (1 - (l1 s1) / (l2 s2)) 0.5, then d_c < 0 ? 0 : (d_c > 1 ? 1 : d_c)  (a NaN passes)
+ *   rho(p) = ((d_0 + d_1) + d_2) / float(C)
+ * Inputs are never written; neither the warped image nor a pooled tensor is.
+ *
+ * ofl_flow_ssim_workspace_bytes(n, h, w, window): bytes of the workspace of ofl_flow_ssim_f64 (8-byte aligned; every word the second
+ *   launch reads is written by the first: nothing to clear), or OFL_E_ARG for sizes that call rejects.
+ *
+ * ofl_flow_ssim_f64: records (optional) float64 [n, OFL_SSIM_RECORD], per image over its known pixels
+ *     [0] count   [1] sum rho   [2] max rho (0 without a known pixel; a NaN is never the max)   [3] sum n(p)   [4 .. 7] 0.
+ *   [0] and [3] are exact.  The sum is the float64 sum of the fp32 rho in a fixed order -- a lane's pixels ascending, the lanes of a
+ *   wave by a butterfly, the waves and then the blocks of an image in index order -- and the number of blocks depends on (h, w) only:
+ *   no float atomics, an image's record has the same bits in any batch and on any run.  ssim_map (optional) fp32 [n,h,w]: rho, +0 where
+ *   the pixel is not known.  At least one of the two must be given; the workspace is needed (and touched) only with records.  Every
+ *   element of every output given is WRITTEN.  One launch, two with records: ofl_last_kernel_name() then names flow_ssim_finish_kernel.
+ *
+ * ofl_flow_ssim_grad_f32: the backward of the per-image mean sum / count with respect to the flow vectors; the clamp is taken as the
+ *   identity.  scale fp32 [n] DEVICE memory (the upstream gradient / count); grad fp32 [n,2,h,w], every element written.  In float64 on
+ *   the fp32 X, Y of the forward, mu, sigma, A = l1, D = l2, B = s1, E = s2 re-formed in float64 by the same two walks; per known centre
+ *   p and channel
+ *     a0 = (2/n) (B muy / (D E) - A B mux / (D^2 E) - A muy / (D E) + A B mux / (D E^2))   a1 = (2/n) A / (D E)   a2 = -(2/n) A B / (D E^2)
+ *     dL/dX_c(x) = -scale / (2 C) (S0(x) + S1(x) Y_c(x) + S2(x) X_c(x)),  S_k(x) the sum of a_k(p) over the known p within R of x
+ *   grad_u(x) = float(sum_c dL/dX_c(x) (-flow_sign) gx_c(x)) with gx_c, gy_c as in ofl_flow_photometric_grad_f32; exactly 0 where the
+ *   pixel is not known.  One launch that runs the channels one after the other through the same LDS: no workspace, no scatter, no
+ *   atomics.  The images carry no gradient.
+ *
+ * OFL_E_ARG, before any launch, for: n outside 1 .. 65535, h or w < 2, h * w >= 2^31, a flow_sign other than +-1, C other than 1 or 3,
+ * a window other than 3, 5 or 7, c1 or c2 not positive or not finite, a NULL flow, img, other, scale or grad pointer, map and records
+ * both NULL, records without a workspace, a negative stride, a flag that is neither 0 nor 1, a pointer not aligned to its element
+ * (workspace, records: 8 bytes).
+ */
+#define OFL_SSIM_RECORD 8
+int64_t ofl_flow_ssim_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t window);
+int ofl_flow_ssim_f64(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, const void* img,
+                      int64_t img_bs, const void* other, int64_t other_bs, int32_t channels, int32_t img_u8, float flow_sign,
+                      int32_t window, float c1, float c2, void* workspace, float* ssim_map, double* records, int32_t n, int32_t h,
+                      int32_t w, void* stream);
+int ofl_flow_ssim_grad_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, const void* img,
+                           int64_t img_bs, const void* other, int64_t other_bs, int32_t channels, int32_t img_u8, float flow_sign,
+                           int32_t window, float c1, float c2, const float* scale, float* grad, int32_t n, int32_t h, int32_t w,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ implemented (`once_differentiable` raises).
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _census, _native, _photometric, _smoothness
+from . import _census, _native, _photometric, _smoothness, _ssim
 
 
 def _reduce_to(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
@@ -302,3 +302,27 @@ class CensusFn(torch.autograd.Function):
         scale = (g.to(rec.device, torch.float64) / rec[:, 0]).to(torch.float32)                      # on the device: nothing is read back
         grad = _census.flow_census_grad(vecs.detach(), mask, img, other, flow_sign, patch, thresh, eps, q, scale)
         return _reduce_to(grad, vecs), None, None, None, None, None, None, None, None
+
+
+class SsimFn(torch.autograd.Function):
+    """ssim[n] = mean over the known pixels of the SSIM penalty between `img` and `other` sampled where the flow points (Flow.ssim,
+    DESIGN.md 3.22): fp32, rounded once from the float64 quotient of the kernel's sum and count; NaN for an image without a known pixel,
+    whose gradient is 0.  Differentiable with respect to the vectors only: the images carry no gradient.  An fp16-stored flow is saved
+    as it is stored."""
+
+    @staticmethod
+    def forward(ctx, vecs, mask, img, other, flow_sign, window, c1, c2):
+        img, other = img.detach(), other.detach()
+        rec, _ = _ssim.flow_ssim(vecs.detach(), mask, img, other, flow_sign, window, c1, c2)
+        ctx.save_for_backward(vecs, mask, img, other, rec)
+        ctx.params = (flow_sign, window, c1, c2)
+        return _ssim.mean_of(rec)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        vecs, mask, img, other, rec = ctx.saved_tensors
+        flow_sign, window, c1, c2 = ctx.params
+        scale = (g.to(rec.device, torch.float64) / rec[:, 0]).to(torch.float32)                      # on the device: nothing is read back
+        grad = _ssim.flow_ssim_grad(vecs.detach(), mask, img, other, flow_sign, window, c1, c2, scale)
+        return _reduce_to(grad, vecs), None, None, None, None, None, None, None

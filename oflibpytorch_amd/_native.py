@@ -39,7 +39,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_flow_consistency_workspace_bytes", "ofl_flow_consistency_f32",     # (these two: declared and bound by _consistency.py)
             "ofl_flow_smoothness_workspace_bytes", "ofl_flow_smoothness_f64", "ofl_flow_smoothness_grad_f32",     # (_smoothness.py)
             "ofl_flow_photometric_workspace_bytes", "ofl_flow_photometric_f64", "ofl_flow_photometric_grad_f32",  # (_photometric.py)
-            "ofl_flow_census_workspace_bytes", "ofl_flow_census_f64", "ofl_flow_census_grad_f32")                 # (_census.py)
+            "ofl_flow_census_workspace_bytes", "ofl_flow_census_f64", "ofl_flow_census_grad_f32",                 # (_census.py)
+            "ofl_flow_ssim_workspace_bytes", "ofl_flow_ssim_f64", "ofl_flow_ssim_grad_f32")                       # (_ssim.py)
 _lib = None
 _load_lock = threading.RLock()
 

@@ -1,0 +1,103 @@
+"""ctypes binding of the fused SSIM loss (ofl_ssim.hip; C ABI: include/oflib_hip.h).
+
+A module of its own next to `_native`, whose helpers it uses: it declares the three entry points it calls and allocates its outputs and
+its workspace under its own module-level name `torch`, which the dirty-memory tests replace (tests/test_gpu_ssim_dirty_memory.py).
+"""
+import ctypes
+
+import torch
+
+from ._native import _check, _on, _planes, _ptr, _stream, _vis_flow, _wants_grad, device, load_library
+
+RECORD = 8                    # doubles per image: count of known pixels, sum rho, max rho, sum of n(p) over the known pixels, 0, 0, 0, 0
+WINDOW, C1, C2 = 3, 1e-4, 9e-4                      # the defaults (0.01^2 and 0.03^2 on the scale 0 .. 1: ARFlow's, monodepth's, UFlow's)
+
+_declared = None
+
+
+def _library():
+    """libofl_hip.so with the three entry points of this module declared."""
+    global _declared
+    lib = load_library()
+    if _declared is not lib:
+        p, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+        lib.ofl_flow_ssim_workspace_bytes.argtypes = [i32, i32, i32, i32]
+        lib.ofl_flow_ssim_workspace_bytes.restype = ctypes.c_int64
+        lib.ofl_flow_ssim_f64.argtypes = [p, i64, i32, p, i64, p, i64, p, i64, i32, i32, f32, i32, f32, f32, p, p, p, i32, i32, i32, p]
+        lib.ofl_flow_ssim_f64.restype = ctypes.c_int
+        lib.ofl_flow_ssim_grad_f32.argtypes = [p, i64, i32, p, i64, p, i64, p, i64, i32, i32, f32, i32, f32, f32, p, p, i32, i32, i32, p]
+        lib.ofl_flow_ssim_grad_f32.restype = ctypes.c_int
+        _declared = lib
+    return lib
+
+
+def _operands(vecs, mask, img, other, dev, n):
+    """(tensors to keep alive, the arguments of both entry points up to img_u8).  `img`, `other`: C-H-W (broadcast over the batch) or
+    N-C-H-W, both float32 or both uint8, the same C (1 or 3)."""
+    v, vbs, half = _vis_flow(vecs, dev, n)
+    m, mbs = (None, 0) if mask is None else _planes(mask, dev, torch.bool, n, "mask")
+    if img.dtype not in (torch.float32, torch.uint8) or other.dtype != img.dtype:
+        raise TypeError("oflibpytorch_amd: the two images need to be both float32 or both uint8")
+    if img.shape[-3] != other.shape[-3]:
+        raise ValueError("oflibpytorch_amd: the two images need the same number of channels")
+    im, ot = img.detach(), other.detach()
+    im, ibs = _planes(im[None] if im.dim() == 3 else im, dev, img.dtype, n, "image")
+    ot, obs = _planes(ot[None] if ot.dim() == 3 else ot, dev, img.dtype, n, "other image")
+    return (v, m, im, ot), (_ptr(v), vbs, half, _ptr(m), mbs, _ptr(im), ibs, _ptr(ot), obs, int(im.shape[1]),
+                            int(img.dtype == torch.uint8))
+
+
+def flow_ssim(vecs: torch.Tensor, mask: torch.Tensor, img: torch.Tensor, other: torch.Tensor, flow_sign: float = -1.0,
+              window: int = WINDOW, c1: float = C1, c2: float = C2, want_map: bool = False, want_record: bool = True):
+    """The SSIM records of a flow (ofl_flow_ssim_f64): vectors [N,2,H,W] fp32 or fp16 as stored, mask [N,H,W] bool or
+    None (all True), `img` the frame on the flow's grid and `other` the frame it points into, [N,C,H,W] or [C,H,W], C 1 or 3, float32
+    or uint8, `flow_sign` -1 for 's' flows and +1 for 't' flows, `window` 3, 5 or 7.  Returns (float64 [N,8] records or None, fp32
+    [N,H,W] map or None) on the HIP device; nothing is read back."""
+    lib, dev = _library(), device(vecs, mask, img, other)
+    n, _, h, w = vecs.shape
+    if not (want_map or want_record):
+        raise ValueError("oflibpytorch_amd: flow_ssim needs at least one output")
+    with _on(dev):
+        keep, args = _operands(vecs, mask, img, other, dev, n)
+        ws = rec = None
+        if want_record:
+            nbytes = int(lib.ofl_flow_ssim_workspace_bytes(n, h, w, int(window)))
+            _check(min(nbytes, 0), "ofl_flow_ssim_workspace_bytes")
+            ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+            rec = torch.empty((n, RECORD), dtype=torch.float64, device=dev)
+        smap = torch.empty((n, h, w), dtype=torch.float32, device=dev) if want_map else None
+        _check(lib.ofl_flow_ssim_f64(*args, float(flow_sign), int(window), float(c1), float(c2), _ptr(ws), _ptr(smap), _ptr(rec), n, h, w,
+                                     _stream(dev)), "ofl_flow_ssim_f64")
+    del keep
+    return rec, smap
+
+
+def flow_ssim_grad(vecs: torch.Tensor, mask: torch.Tensor, img: torch.Tensor, other: torch.Tensor, flow_sign: float, window: int,
+                   c1: float, c2: float, scale: torch.Tensor) -> torch.Tensor:
+    """The backward of the per-image mean SSIM penalty (ofl_flow_ssim_grad_f32): `scale` fp32 [N] on the device (upstream gradient /
+    count).  Returns the gradient with respect to the vectors, fp32 [N,2,H,W] on the HIP device."""
+    lib, dev = _library(), device(vecs, mask, img, other)
+    n, _, h, w = vecs.shape
+    with _on(dev):
+        keep, args = _operands(vecs, mask, img, other, dev, n)
+        sc = scale.detach().to(dev, torch.float32).contiguous()
+        grad = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+        _check(lib.ofl_flow_ssim_grad_f32(*args, float(flow_sign), int(window), float(c1), float(c2), _ptr(sc), _ptr(grad), n, h, w,
+                                          _stream(dev)), "ofl_flow_ssim_grad_f32")
+    del keep
+    return grad
+
+
+def mean_of(rec: torch.Tensor) -> torch.Tensor:
+    """The loss of a record: the float64 quotient sum / count rounded once to fp32 (NaN without a known pixel)."""
+    return (rec[:, 1] / rec[:, 0]).to(torch.float32)
+
+
+def ssim(vecs: torch.Tensor, mask: torch.Tensor, img: torch.Tensor, other: torch.Tensor, flow_sign: float = -1.0, window: int = WINDOW,
+         c1: float = C1, c2: float = C2) -> torch.Tensor:
+    """The per-image SSIM loss, fp32 [N].  When autograd is recording and the vectors require a gradient, the call goes through
+    `_autograd.SsimFn`; the images never carry a gradient."""
+    if _wants_grad(vecs):
+        from . import _autograd
+        return _autograd.SsimFn.apply(vecs, mask, img, other, flow_sign, window, c1, c2)
+    return mean_of(flow_ssim(vecs, mask, img, other, flow_sign, window, c1, c2)[0])

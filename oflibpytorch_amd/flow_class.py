@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _census, _consistency, _native, _photometric, _smoothness, distributed
+from . import _census, _consistency, _native, _photometric, _smoothness, _ssim, distributed
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
@@ -1564,6 +1564,100 @@ class Flow(object):
         the census term of an unsupervised flow loss.  The images carry no gradient, even if they require one; an element without a
         known pixel has gradient 0.  The backward pass gathers (no atomics): it is bitwise reproducible."""
         return _census.census(*self._census_operands(img, other, patch, thresh, eps, q, consider_mask)).to(self._device)
+
+    # ------------------------------------------------------------------------------------------
+    # SSIM loss (DESIGN.md 3.22; an extension: the reference has no such methods)
+    # ------------------------------------------------------------------------------------------
+    def _ssim_operands(self, img, other, window, c1, c2, consider_mask: bool):
+        """The checks the three SSIM methods share; returns the arguments of `_ssim.flow_ssim` up to c2."""
+        err = "Error computing SSIM loss: "
+        images = []
+        for name, im in (("Img", img), ("Other", other)):
+            if isinstance(im, np.ndarray):
+                if im.dtype not in (np.float32, np.uint8):
+                    raise TypeError(err + name + " needs to be of dtype float32 or uint8")
+                im = torch.from_numpy(im)
+            if not isinstance(im, torch.Tensor):
+                raise TypeError(err + name + " needs to be a torch tensor or a numpy array")
+            if im.dtype not in (torch.float32, torch.uint8):
+                raise TypeError(err + name + " needs to be of dtype float32 or uint8")
+            images.append(im)
+        img, other = images
+        if img.dtype != other.dtype:
+            raise TypeError(err + "Img and other need to be of the same dtype")
+        for name, im in (("Img", img), ("Other", other)):
+            if im.dim() not in (3, 4):
+                raise ValueError(err + name + " needs to have 3 or 4 dimensions, C-H-W or N-C-H-W")
+            if im.shape[-3] not in (1, 3):
+                raise ValueError(err + name + " needs to have 1 or 3 channels")
+        if img.shape[-3] != other.shape[-3]:
+            raise ValueError(err + "Img and other need to have the same number of channels")
+        for name, im in (("Img", img), ("Other", other)):
+            if tuple(im.shape[-2:]) != tuple(self.shape[1:]):
+                raise ValueError(err + name + " needs to have the H-W shape of the flow")
+            if im.dim() == 4 and im.shape[0] != self.shape[0]:
+                raise ValueError(err + name + " needs to have the batch size of the flow")
+        if self.shape[1] < 2 or self.shape[2] < 2:
+            raise ValueError(err + "Flow field needs to be at least 2 pixels high and wide")
+        window = _ssim.WINDOW if window is None else window
+        if not isinstance(window, int) or isinstance(window, bool):
+            raise TypeError(err + "Window needs to be an integer")
+        if window not in (3, 5, 7):
+            raise ValueError(err + "Window needs to be 3, 5 or 7")
+        values = []
+        for name, val, default in (("C1", c1, _ssim.C1), ("C2", c2, _ssim.C2)):
+            val = default if val is None else val
+            if not isinstance(val, (int, float)) or isinstance(val, bool):
+                raise TypeError(err + name + " needs to be an integer or a float")
+            # (the kernels take float32: a value that rounds to 0 or to infinity there is out of range)
+            if not (math.isfinite(val) and val > 0 and 0 < float(np.float32(val)) < float('inf')):
+                raise ValueError(err + name + " needs to be finite and larger than 0")
+            values.append(float(val))
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError(err + "Consider_mask needs to be boolean")
+        images = []
+        for im in (img, other):
+            im = im.detach()
+            if im.device != self._device:
+                im = im.to(self._device)
+            images.append(im.contiguous())
+        return (self._fv, (self._mask if consider_mask else None), images[0], images[1], -1.0 if self._ref == 's' else 1.0,
+                window, values[0], values[1])
+
+    def ssim_stats(self, img, other, window: int = None, c1: float = None, c2: float = None, consider_mask: bool = None) -> dict:
+        """The structural-similarity penalty of this flow between two frames, per batch element: the data term ARFlow, UFlow and the
+        monodepth line weight against the brightness difference.  `img` is the frame on the flow's own grid, `other` the frame the
+        flow points into, as in :meth:`photometric_stats`: tensors or arrays of one dtype, float32 (scale 0 .. 1) or uint8 (read as
+        s / 255), C-H-W or N-C-H-W with the same 1 or 3 channels.  `other` is sampled bilinearly where the flow points; per channel,
+        over the `window` x `window` box around a pixel (3, 5 or 7, default 3), the means, variances and the covariance of the two
+        frames give SSIM = (2 mx my + `c1`) (2 sxy + `c2`) / ((mx^2 + my^2 + `c1`) (sxx + syy + `c2`)), `c1` default 1e-4, `c2`
+        default 9e-4, and the penalty of the pixel is the mean over the channels of clamp((1 - SSIM) / 2, 0, 1).  A pixel is USABLE
+        where it is valid in this flow's mask (with `consider_mask` False: everywhere) and its sample's taps lie in the frame; a
+        window holds its usable pixels only and is normalised by their number, and a pixel is KNOWN where it is usable.  Returns a
+        dict of tensors on the flow's device: 'count' int64 [N], the known pixels; 'sum', 'max' float64 [N] over them; 'ssim' float64
+        [N], sum / count, NaN without a known pixel; 'fill' float64 [N], the share of the window pixels of the known pixels that were
+        usable.  One pass of ofl_ssim.hip from LDS tiles: neither the warped image nor a pooled tensor is written, float64 sums in a
+        fixed order (bitwise reproducible, independent of the batch), nothing is read back to the host.  Not
+        differentiable: see :meth:`ssim`."""
+        ops = self._ssim_operands(img, other, window, c1, c2, consider_mask)
+        rec, _ = _ssim.flow_ssim(*ops)
+        rec = rec.to(self._device)
+        return {'count': rec[:, 0].to(torch.int64), 'sum': rec[:, 1].clone(), 'max': rec[:, 2].clone(), 'ssim': rec[:, 1] / rec[:, 0],
+                'fill': rec[:, 3] / (rec[:, 0] * float(ops[5] * ops[5]))}
+
+    def ssim_map(self, img, other, window: int = None, c1: float = None, c2: float = None, consider_mask: bool = None) -> torch.Tensor:
+        """The penalty of :meth:`ssim_stats` at every pixel: float32 N-H-W on the flow's device, 0 where the pixel is not known (the
+        kernel writes nothing else).  Not differentiable: see :meth:`ssim`."""
+        ops = self._ssim_operands(img, other, window, c1, c2, consider_mask)
+        return _ssim.flow_ssim(*ops, want_map=True, want_record=False)[1].to(self._device)
+
+    def ssim(self, img, other, window: int = None, c1: float = None, c2: float = None, consider_mask: bool = None) -> torch.Tensor:
+        """The mean of :meth:`ssim_stats` over the known pixels per batch element: float32 [N] on the flow's device (the float64
+        quotient rounded once; NaN for an element without a known pixel).  Differentiable with respect to the flow vectors ONLY --
+        the SSIM term of an unsupervised flow loss.  The images carry no gradient, even if they require one; an element without a
+        known pixel has gradient 0.  The backward pass gathers (no atomics): it is bitwise reproducible."""
+        return _ssim.ssim(*self._ssim_operands(img, other, window, c1, c2, consider_mask)).to(self._device)
 
     # ------------------------------------------------------------------------------------------
     # composition (flow_class.py:1648-1810)

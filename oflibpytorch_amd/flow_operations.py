@@ -149,6 +149,21 @@ def flow_census_stats(flow, img, other, ref: str, mask=None, patch: int = None, 
     return stats if len(flow.shape) > 3 else {k: v.squeeze(0) for k, v in stats.items()}
 
 
+def flow_ssim(flow, img, other, ref: str, mask=None, window: int = None, c1: float = None, c2: float = None) -> torch.Tensor:
+    """Flow(flow, ref, mask).ssim(img, other, window, c1, c2): the SSIM loss between the frame `img` on the flow's grid and the frame
+    `other` it points into, float32 [N] (a scalar tensor for 3-D input), differentiable with respect to a tensor `flow`.  An extension
+    (DESIGN.md 3.22): the reference has no such function."""
+    s = Flow(flow, ref, mask).ssim(img, other, window=window, c1=c1, c2=c2)
+    return s if len(flow.shape) > 3 else s.squeeze(0)
+
+
+def flow_ssim_stats(flow, img, other, ref: str, mask=None, window: int = None, c1: float = None, c2: float = None) -> dict:
+    """Flow(flow, ref, mask).ssim_stats(img, other, window, c1, c2): the dict of Flow.ssim_stats for arrays / tensors (N-)2-H-W or
+    (N-)H-W-2 with an optional mask (N-)H-W; 3-D in -> entries without the batch dimension.  An extension."""
+    stats = Flow(flow, ref, mask).ssim_stats(img, other, window=window, c1=c1, c2=c2)
+    return stats if len(flow.shape) > 3 else {k: v.squeeze(0) for k, v in stats.items()}
+
+
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
     """Concatenate flow objects of equal H, W, ref and device along the batch axis (flow_operations.py:458-483)"""
     if not isinstance(flows, (list, tuple)):
