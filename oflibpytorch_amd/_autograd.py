@@ -256,73 +256,44 @@ class SmoothnessFn(torch.autograd.Function):
         return _reduce_to(grad, vecs), None, None, None, None, None
 
 
-class PhotometricFn(torch.autograd.Function):
-    """photometric[n] = mean over the known pixels of the Charbonnier penalty between `img` and `other` sampled where the flow points
-    (Flow.photometric): fp32, rounded once from the float64 quotient of the kernel's sum and count; NaN for an image
-    without a known pixel, whose gradient is 0.  Differentiable with respect to the vectors only: the images carry no gradient.  An
-    fp16-stored flow is saved as it is stored."""
+class _PairLossFn(torch.autograd.Function):
+    """loss[n] = mean over the known pixels of a penalty between `img` and `other` sampled where the flow points (the image-pair losses,
+    DESIGN.md 3.20 to 3.22): fp32, rounded once from the float64 quotient of the kernel's sum and count; NaN for an image without a known
+    pixel, whose gradient is 0.  Differentiable with respect to the vectors only: the images carry no gradient.  An fp16-stored flow is
+    saved as it is stored.  A subclass names its binding: the module and its two functions.  They are looked up by name at every call,
+    not held as callables, because the host tests replace `module.flow_*` with fakes after this class exists; forward and backward
+    are static, so the subclass is reached through `ctx._forward_cls`, which torch sets on the context class of every Function."""
+    binding = None                                 # (module, name of flow_*, name of flow_*_grad)
 
     @staticmethod
-    def forward(ctx, vecs, mask, img, other, flow_sign, eps):
+    def forward(ctx, vecs, mask, img, other, *params):
+        module, fwd, _ = ctx._forward_cls.binding
         img, other = img.detach(), other.detach()
-        rec, _ = _photometric.flow_photometric(vecs.detach(), mask, img, other, flow_sign, eps)
+        rec, _ = getattr(module, fwd)(vecs.detach(), mask, img, other, *params)
         ctx.save_for_backward(vecs, mask, img, other, rec)
-        ctx.params = (flow_sign, eps)
-        return _photometric.mean_of(rec)
+        ctx.params = params
+        return _native.mean_of(rec)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
         vecs, mask, img, other, rec = ctx.saved_tensors
-        flow_sign, eps = ctx.params
+        module, _, bwd = ctx._forward_cls.binding
         scale = (g.to(rec.device, torch.float64) / rec[:, 0]).to(torch.float32)                      # on the device: nothing is read back
-        grad = _photometric.flow_photometric_grad(vecs.detach(), mask, img, other, flow_sign, eps, scale)
-        return _reduce_to(grad, vecs), None, None, None, None, None
+        grad = getattr(module, bwd)(vecs.detach(), mask, img, other, *ctx.params, scale)
+        return (_reduce_to(grad, vecs), None, None, None) + (None,) * len(ctx.params)
 
 
-class CensusFn(torch.autograd.Function):
-    """census[n] = mean over the known pixels of the census penalty between `img` and `other` sampled where the flow points
-    (Flow.census): fp32, rounded once from the float64 quotient of the kernel's sum and count; NaN for an image without
-    a known pixel, whose gradient is 0.  Differentiable with respect to the vectors only: the images carry no gradient.  An fp16-stored
-    flow is saved as it is stored."""
-
-    @staticmethod
-    def forward(ctx, vecs, mask, img, other, flow_sign, patch, thresh, eps, q):
-        img, other = img.detach(), other.detach()
-        rec, _ = _census.flow_census(vecs.detach(), mask, img, other, flow_sign, patch, thresh, eps, q)
-        ctx.save_for_backward(vecs, mask, img, other, rec)
-        ctx.params = (flow_sign, patch, thresh, eps, q)
-        return _census.mean_of(rec)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        vecs, mask, img, other, rec = ctx.saved_tensors
-        flow_sign, patch, thresh, eps, q = ctx.params
-        scale = (g.to(rec.device, torch.float64) / rec[:, 0]).to(torch.float32)                      # on the device: nothing is read back
-        grad = _census.flow_census_grad(vecs.detach(), mask, img, other, flow_sign, patch, thresh, eps, q, scale)
-        return _reduce_to(grad, vecs), None, None, None, None, None, None, None, None
+class PhotometricFn(_PairLossFn):
+    """photometric[n]: the Charbonnier penalty (Flow.photometric); params: flow_sign, eps"""
+    binding = (_photometric, "flow_photometric", "flow_photometric_grad")
 
 
-class SsimFn(torch.autograd.Function):
-    """ssim[n] = mean over the known pixels of the SSIM penalty between `img` and `other` sampled where the flow points (Flow.ssim,
-    DESIGN.md 3.22): fp32, rounded once from the float64 quotient of the kernel's sum and count; NaN for an image without a known pixel,
-    whose gradient is 0.  Differentiable with respect to the vectors only: the images carry no gradient.  An fp16-stored flow is saved
-    as it is stored."""
+class CensusFn(_PairLossFn):
+    """census[n]: the census penalty (Flow.census); params: flow_sign, patch, thresh, eps, q"""
+    binding = (_census, "flow_census", "flow_census_grad")
 
-    @staticmethod
-    def forward(ctx, vecs, mask, img, other, flow_sign, window, c1, c2):
-        img, other = img.detach(), other.detach()
-        rec, _ = _ssim.flow_ssim(vecs.detach(), mask, img, other, flow_sign, window, c1, c2)
-        ctx.save_for_backward(vecs, mask, img, other, rec)
-        ctx.params = (flow_sign, window, c1, c2)
-        return _ssim.mean_of(rec)
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g):
-        vecs, mask, img, other, rec = ctx.saved_tensors
-        flow_sign, window, c1, c2 = ctx.params
-        scale = (g.to(rec.device, torch.float64) / rec[:, 0]).to(torch.float32)                      # on the device: nothing is read back
-        grad = _ssim.flow_ssim_grad(vecs.detach(), mask, img, other, flow_sign, window, c1, c2, scale)
-        return _reduce_to(grad, vecs), None, None, None, None, None, None, None
+class SsimFn(_PairLossFn):
+    """ssim[n]: the SSIM penalty (Flow.ssim); params: flow_sign, window, c1, c2"""
+    binding = (_ssim, "flow_ssim", "flow_ssim_grad")

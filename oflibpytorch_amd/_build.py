@@ -14,7 +14,8 @@ SOURCES = [os.path.join(_PKG, "csrc", "ofl_kernels.hip"), os.path.join(_PKG, "cs
            os.path.join(_PKG, "csrc", "ofl_ssim.hip"),
            # plain C++ host code (the PNG unfilter of the dataset loaders): no device code in it, linked into the same library
            os.path.join(_PKG, "csrc", "ofl_png_host.cpp")]
-HEADERS = [os.path.join(_ROOT, "include", "oflib_hip.h")]
+# [0]: the C ABI; then the internal headers, which the sources include by relative path
+HEADERS = [os.path.join(_ROOT, "include", "oflib_hip.h"), os.path.join(_PKG, "csrc", "ofl_loss_common.hpp")]
 LIB_PATH = os.path.join(_PKG, "libofl_hip.so")
 
 # -ffp-contract=off / -fno-fast-math: the kernels restate the reference's fp32 operation order;

@@ -7,7 +7,7 @@ import ctypes
 
 import torch
 
-from ._native import _check, _on, _planes, _ptr, _stream, _vis_flow, _wants_grad, device, load_library
+from ._native import _check, _on, _operands, _ptr, _stream, _wants_grad, device, load_library, mean_of
 
 RECORD = 8                    # doubles per image: count of known pixels, sum rho, max rho, sum of n(p) over the known pixels, 0, 0, 0, 0
 PATCH, THRESH, EPS, Q = 7, 0.1, 0.01, 0.4           # the defaults (UFlow's)
@@ -29,22 +29,6 @@ def _library():
         lib.ofl_flow_census_grad_f32.restype = ctypes.c_int
         _declared = lib
     return lib
-
-
-def _operands(vecs, mask, img, other, dev, n):
-    """(tensors to keep alive, the arguments of both entry points up to img_u8).  `img`, `other`: C-H-W (broadcast over the batch) or
-    N-C-H-W, both float32 or both uint8, the same C (1 or 3)."""
-    v, vbs, half = _vis_flow(vecs, dev, n)
-    m, mbs = (None, 0) if mask is None else _planes(mask, dev, torch.bool, n, "mask")
-    if img.dtype not in (torch.float32, torch.uint8) or other.dtype != img.dtype:
-        raise TypeError("oflibpytorch_amd: the two images need to be both float32 or both uint8")
-    if img.shape[-3] != other.shape[-3]:
-        raise ValueError("oflibpytorch_amd: the two images need the same number of channels")
-    im, ot = img.detach(), other.detach()
-    im, ibs = _planes(im[None] if im.dim() == 3 else im, dev, img.dtype, n, "image")
-    ot, obs = _planes(ot[None] if ot.dim() == 3 else ot, dev, img.dtype, n, "other image")
-    return (v, m, im, ot), (_ptr(v), vbs, half, _ptr(m), mbs, _ptr(im), ibs, _ptr(ot), obs, int(im.shape[1]),
-                            int(img.dtype == torch.uint8))
 
 
 def flow_census(vecs: torch.Tensor, mask: torch.Tensor, img: torch.Tensor, other: torch.Tensor, flow_sign: float = -1.0,
@@ -87,11 +71,6 @@ def flow_census_grad(vecs: torch.Tensor, mask: torch.Tensor, img: torch.Tensor, 
                                             _ptr(grad), n, h, w, _stream(dev)), "ofl_flow_census_grad_f32")
     del keep
     return grad
-
-
-def mean_of(rec: torch.Tensor) -> torch.Tensor:
-    """The loss of a record: the float64 quotient sum / count rounded once to fp32 (NaN without a known pixel)."""
-    return (rec[:, 1] / rec[:, 0]).to(torch.float32)
 
 
 def census(vecs: torch.Tensor, mask: torch.Tensor, img: torch.Tensor, other: torch.Tensor, flow_sign: float = -1.0, patch: int = PATCH,

@@ -1284,6 +1284,27 @@ def _vis_flow(vecs: torch.Tensor, dev, n: int):
     return v, vbs, 0
 
 
+def _operands(vecs, mask, img, other, dev, n):
+    """The operands the image-pair losses share (_photometric, _census, _ssim): (tensors to keep alive, the arguments of both entry
+    points up to img_u8).  `img`, `other`: C-H-W (broadcast over the batch) or N-C-H-W, both float32 or both uint8, the same C."""
+    v, vbs, half = _vis_flow(vecs, dev, n)
+    m, mbs = (None, 0) if mask is None else _planes(mask, dev, torch.bool, n, "mask")
+    if img.dtype not in (torch.float32, torch.uint8) or other.dtype != img.dtype:
+        raise TypeError("oflibpytorch_amd: the two images need to be both float32 or both uint8")
+    if img.shape[-3] != other.shape[-3]:
+        raise ValueError("oflibpytorch_amd: the two images need the same number of channels")
+    im, ot = img.detach(), other.detach()
+    im, ibs = _planes(im[None] if im.dim() == 3 else im, dev, img.dtype, n, "image")
+    ot, obs = _planes(ot[None] if ot.dim() == 3 else ot, dev, img.dtype, n, "other image")
+    return (v, m, im, ot), (_ptr(v), vbs, half, _ptr(m), mbs, _ptr(im), ibs, _ptr(ot), obs, int(im.shape[1]),
+                            int(img.dtype == torch.uint8))
+
+
+def mean_of(rec: torch.Tensor) -> torch.Tensor:
+    """The loss of a record of an image-pair loss: the float64 quotient sum / count rounded once to fp32 (NaN without a known pixel)."""
+    return (rec[:, 1] / rec[:, 0]).to(torch.float32)
+
+
 def visualise_range(vecs: torch.Tensor, mask: torch.Tensor = None):
     """The default `range_max` of Flow.visualise (flow_class.py:1300-1309) on the device: per image the 99th percentile of the
     thresholded magnitudes (all pixels, or those under `mask`), else their max, else 1 (ofl_visualise_range_f32).  Returns

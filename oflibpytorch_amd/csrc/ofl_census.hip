@@ -14,11 +14,10 @@
 //                                              (float64), then every pixel gathers dL/dGw over its patch and multiplies by the derivative
 //                                              of its own sample: no scatter, no atomics, no workspace
 //
-// The warped image is never written, nor any tensor of patch^2 - 1 channels.  The sample position, the tap weights and the four-term
-// sums RESTATE unnormalise() and the body of warp_bwd_kernel of ofl_kernels.hip as ofl_photometric.hip does (position unnormalise(grid -
-// flow_sign * a), floorf, nw / ne / sw / se, `v_nw * nw` then three fmaf in the order ne, sw, se, the same chain over the taps'
-// insideness for mr; a tap outside the frame reads as 0) -- a change there is made here too; tests/test_gpu_census.py compares the two
-// on the device.  Taps are single loads straight from global memory at offsets clamped into the plane: always addressable.
+// The warped image is never written, nor any tensor of patch^2 - 1 channels.  The sample (position, taps, weights, the four-term sums and mr) is
+// the one of ofl_loss_common.hpp, which restates the backward warp of ofl_kernels.hip; tests/test_gpu_census.py compares the two on the
+// device.  A uint8 sample stays on the scale 0 .. 255 here (ld_img_raw).  Taps are single loads straight from global memory at offsets
+// clamped into the plane: always addressable.
 //
 // The tile.  A pixel of the staged region costs a warp (two flow loads, a mask byte, 4 taps x C planes, the position chain with its two
 // divisions); the walk costs patch^2 - 1 terms of three divisions and two roots each and dominates.  64 x 16 outputs over 70 x 22 staged
@@ -29,23 +28,12 @@
 // 70 x 22 float64 kappa, 31 472 B.
 // 256 threads, four pixels per lane (rows ly, ly + 4, ly + 8, ly + 12 of the tile), so that a wave's map store is one run of 256 bytes.
 //
-// Sums as in ofl_metrics.hip: the number of blocks depends on (h, w) only, a lane adds its pixels in ascending order, lanes by a
-// butterfly, waves and then blocks in index order: no float atomics, the record of an image carries the same bits in any batch and on
-// any run.  C ABI: include/oflib_hip.h.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "oflib_hip.h"
-
-#pragma clang fp contract(off)
-
-// the launch recorder of ofl_kernels.hip (ofl_last_kernel_name)
-extern const void* g_ofl_last_kernel;
-#define OFL_KLAUNCH(K, ...) do { g_ofl_last_kernel = (const void*)(K); hipLaunchKernelGGL(K, __VA_ARGS__); } while (0)
+// The sums are those of ofl_loss_common.hpp; the number of blocks depends on (h, w) only.  C ABI: include/oflib_hip.h.
+#include "ofl_loss_common.hpp"
 
 namespace {
+
+using namespace ofl_loss;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -53,7 +41,6 @@ constexpr int kTileW = 64, kTileH = 16;            // output pixels of a block
 constexpr int kRows = kTileH / kWaves;             // pixels per lane
 constexpr int kChunk = 256;                        // block records the finish kernel stages at a time
 constexpr int kRec = OFL_CENSUS_RECORD;            // doubles per record
-constexpr float kValidThr = 0.99999f;              // ofl_kernels.hip (flow_class.py:922)
 constexpr float kSoft = 0.81f;                     // the constant under the root of the soft sign
 constexpr float kGreyR = 0.299f, kGreyG = 0.587f, kGreyB = 0.114f;
 enum { R_COUNT = 0, R_SUM = 1, R_MAX = 2, R_TERMS = 3, R_USED = 4 };
@@ -75,66 +62,6 @@ struct CensusParams {
     const float* scale;                            // backward: [n]
     float* grad;                                   // backward: [n][2][H*W]
 };
-
-// unnormalise() of ofl_kernels.hip: normalise_coords (utils.py:462-465) followed by the grid sampler's align_corners un-normalise
-__device__ __forceinline__ float unnormalise(float p, float size_m1, float half_size_m1) {
-    float g = p * 2.0f;
-    g = g / size_m1;  // IEEE correctly-rounded divide (no fast-math)
-    g = g - 1.0f;
-    return (g + 1.0f) * half_size_m1;
-}
-
-template <bool HALF>
-__device__ __forceinline__ float ld_flow(const void* base, int64_t i) {
-    return HALF ? __half2float(reinterpret_cast<const __half*>(base)[i]) : reinterpret_cast<const float*>(base)[i];
-}
-
-// one sample of an image plane: a uint8 sample s is float(s), on the scale 0 .. 255
-template <bool U8>
-__device__ __forceinline__ float ld_img(const void* base, int64_t i) {
-    return U8 ? (float)reinterpret_cast<const uint8_t*>(base)[i] : reinterpret_cast<const float*>(base)[i];
-}
-
-// correctly rounded fp32 square root (ofl_metrics.hip)
-__device__ __forceinline__ float sqrt_rn(float s) { return __builtin_sqrtf(s); }
-
-// the four taps of the sample of pixel (x, y) whose vector is (u, v): the head of warp_bwd_kernel (ofl_kernels.hip)
-struct Taps {
-    float sx, sy, x_w, y_n;                        // the position and its floors
-    float nw, ne, sw, se;                          // fp32 weights
-    int64_t o_nw, o_ne, o_sw, o_se;                // offsets in a plane, clamped into it
-    bool k_nw, k_ne, k_sw, k_se;                   // inside the frame
-    float mr;                                      // weight sum of the taps inside
-};
-
-__device__ __forceinline__ Taps taps_of(const CensusParams& p, int x, int y, float u, float v) {
-    Taps t;
-    const int w = p.w, h = p.h;
-    const float px = (float)x - p.flow_sign * u;
-    const float py = (float)y - p.flow_sign * v;
-    t.sx = unnormalise(px, p.wm1, p.half_wm1);
-    t.sy = unnormalise(py, p.hm1, p.half_hm1);
-    t.x_w = floorf(t.sx); t.y_n = floorf(t.sy);
-    const float ww = t.sx - t.x_w, e = 1.0f - ww;
-    const float nn = t.sy - t.y_n, s = 1.0f - nn;
-    t.nw = s * e; t.ne = s * ww; t.sw = nn * e; t.se = nn * ww;
-    const float x_e = t.x_w + 1.0f, y_s = t.y_n + 1.0f;
-    const bool x0ok = (t.x_w > -1.0f) && (t.x_w < (float)w);
-    const bool x1ok = (x_e > -1.0f) && (x_e < (float)w);
-    const bool y0ok = (t.y_n > -1.0f) && (t.y_n < (float)h);
-    const bool y1ok = (y_s > -1.0f) && (y_s < (float)h);
-    const int ix0 = x0ok ? (int)t.x_w : 0, ix1 = x1ok ? (int)x_e : 0;
-    const int iy0 = y0ok ? (int)t.y_n : 0, iy1 = y1ok ? (int)y_s : 0;
-    t.o_nw = (int64_t)iy0 * w + ix0; t.o_ne = (int64_t)iy0 * w + ix1;
-    t.o_sw = (int64_t)iy1 * w + ix0; t.o_se = (int64_t)iy1 * w + ix1;
-    t.k_nw = x0ok && y0ok; t.k_ne = x1ok && y0ok; t.k_sw = x0ok && y1ok; t.k_se = x1ok && y1ok;
-    float mr = (t.k_nw ? 1.0f : 0.0f) * t.nw;
-    mr = __builtin_fmaf(t.k_ne ? 1.0f : 0.0f, t.ne, mr);
-    mr = __builtin_fmaf(t.k_sw ? 1.0f : 0.0f, t.sw, mr);
-    mr = __builtin_fmaf(t.k_se ? 1.0f : 0.0f, t.se, mr);
-    t.mr = mr;
-    return t;
-}
 
 // grey of up to three channel values; float32 images are brought to the scale 0 .. 255
 template <bool U8>
@@ -167,16 +94,12 @@ __device__ __forceinline__ void stage(const CensusParams& p, int64_t n_img, int 
                 for (int c = 0; c < 3; ++c) {
                     if (c < p.chan) {
                         const int64_t pl = oo + (int64_t)c * p.hw;
-                        const float v_nw = t.k_nw ? ld_img<U8>(p.other, pl + t.o_nw) : 0.0f;
-                        const float v_ne = t.k_ne ? ld_img<U8>(p.other, pl + t.o_ne) : 0.0f;
-                        const float v_sw = t.k_sw ? ld_img<U8>(p.other, pl + t.o_sw) : 0.0f;
-                        const float v_se = t.k_se ? ld_img<U8>(p.other, pl + t.o_se) : 0.0f;
-                        float iw = v_nw * t.nw;
-                        iw = __builtin_fmaf(v_ne, t.ne, iw);
-                        iw = __builtin_fmaf(v_sw, t.sw, iw);
-                        iw = __builtin_fmaf(v_se, t.se, iw);
-                        vw[c] = iw;
-                        vi[c] = ld_img<U8>(p.img, io + (int64_t)c * p.hw + pix);
+                        const float v_nw = t.k_nw ? ld_img_raw<U8>(p.other, pl + t.o_nw) : 0.0f;
+                        const float v_ne = t.k_ne ? ld_img_raw<U8>(p.other, pl + t.o_ne) : 0.0f;
+                        const float v_sw = t.k_sw ? ld_img_raw<U8>(p.other, pl + t.o_sw) : 0.0f;
+                        const float v_se = t.k_se ? ld_img_raw<U8>(p.other, pl + t.o_se) : 0.0f;
+                        vw[c] = sample_of(t, v_nw, v_ne, v_sw, v_se);
+                        vi[c] = ld_img_raw<U8>(p.img, io + (int64_t)c * p.hw + pix);
                     }
                 }
                 gw = grey_of<U8>(vw, p.chan);
@@ -257,55 +180,16 @@ __global__ void __launch_bounds__(kThreads) flow_census_kernel(CensusParams p) {
         }
     }
     if (p.partial == nullptr) return;              // (the same for every thread of the launch)
-    // lanes: butterfly (every lane ends with the wave's value); waves: added in index order by the first threads
     double rec[kRec];
 #pragma unroll
     for (int i = 0; i < kRec; ++i) rec[i] = 0.0;
     rec[R_COUNT] = (double)count; rec[R_SUM] = sum; rec[R_MAX] = (double)mx; rec[R_TERMS] = (double)terms;
-#pragma unroll
-    for (int i = 0; i < R_USED; ++i) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double o = __shfl_xor(rec[i], off);
-            rec[i] = (i == R_MAX) ? fmax(rec[i], o) : rec[i] + o;
-        }
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < kRec; ++i) s_red[wave * kRec + i] = rec[i];
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < kRec) {
-        double s = s_red[threadIdx.x];
-        for (int wv = 1; wv < kWaves; ++wv) {
-            const double o = s_red[wv * kRec + threadIdx.x];
-            s = (threadIdx.x == R_MAX) ? fmax(s, o) : s + o;
-        }
-        p.partial[(n_img * p.nblk + blockIdx.x) * kRec + threadIdx.x] = s;
-    }
+    reduce_record<kRec, R_USED, R_MAX, kWaves>(rec, s_red, p.partial, n_img, p.nblk);
 }
 
-// one block per image: the block records staged in LDS by all threads, kChunk at a time (independent loads), then slot
-// i added in ascending block order by thread i
+// one block per image: the block records added in ascending block order, kChunk of them through LDS at a time
 __global__ void __launch_bounds__(kThreads) flow_census_finish_kernel(CensusParams p) {
-    __shared__ double s_part[kChunk * kRec];
-    const int64_t n_img = blockIdx.x;
-    const double* part = p.partial + n_img * p.nblk * kRec;
-    double s = 0.0;
-    for (int base = 0; base < p.nblk; base += kChunk) {
-        const int cnt = p.nblk - base < kChunk ? p.nblk - base : kChunk;
-        for (int i = threadIdx.x; i < cnt * kRec; i += kThreads) s_part[i] = part[(int64_t)base * kRec + i];
-        __syncthreads();
-        if ((int)threadIdx.x < kRec) {
-            for (int b = 0; b < cnt; ++b) {
-                const double o = s_part[b * kRec + threadIdx.x];
-                s = (threadIdx.x == R_MAX) ? fmax(s, o) : s + o;
-            }
-        }
-        __syncthreads();
-    }
-    if ((int)threadIdx.x < kRec) p.out[n_img * kRec + threadIdx.x] = s;
+    finish_records<kRec, R_MAX, kChunk, kThreads>(p.partial, p.nblk, p.out);
 }
 
 template <int PATCH, bool HALF, bool U8>
@@ -379,23 +263,20 @@ __global__ void __launch_bounds__(kThreads) flow_census_grad_kernel(CensusParams
             go[0] = 0.0f; go[p.hw] = 0.0f;
             continue;
         }
-        // the derivative of the pixel's own sample: float64 fractions of the float32 position (tests/grad_oracle64.py)
+        // the derivative of the pixel's own sample
         const float u = ld_flow<HALF>(p.flow, fo + pix), v = ld_flow<HALF>(p.flow, fo + p.hw + pix);
         const Taps t = taps_of(p, x, y, u, v);
-        const double ww = (double)t.sx - (double)t.x_w, e = 1.0 - ww;
-        const double nn = (double)t.sy - (double)t.y_n, s = 1.0 - nn;
         double ax = 0.0, ay = 0.0;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             if (ch < p.chan) {
                 const int64_t pl = oo + (int64_t)ch * p.hw;
-                const double v_nw = t.k_nw ? (double)ld_img<U8>(p.other, pl + t.o_nw) : 0.0;
-                const double v_ne = t.k_ne ? (double)ld_img<U8>(p.other, pl + t.o_ne) : 0.0;
-                const double v_sw = t.k_sw ? (double)ld_img<U8>(p.other, pl + t.o_sw) : 0.0;
-                const double v_se = t.k_se ? (double)ld_img<U8>(p.other, pl + t.o_se) : 0.0;
-                // west taps -1, east taps +1 (north -1, south +1), each times the other axis's weight; a tap outside the frame is 0
-                const double gx = (((-s) * v_nw + s * v_ne) - nn * v_sw) + nn * v_se;
-                const double gy = (((-e) * v_nw - ww * v_ne) + e * v_sw) + ww * v_se;
+                const double v_nw = t.k_nw ? (double)ld_img_raw<U8>(p.other, pl + t.o_nw) : 0.0;
+                const double v_ne = t.k_ne ? (double)ld_img_raw<U8>(p.other, pl + t.o_ne) : 0.0;
+                const double v_sw = t.k_sw ? (double)ld_img_raw<U8>(p.other, pl + t.o_sw) : 0.0;
+                const double v_se = t.k_se ? (double)ld_img_raw<U8>(p.other, pl + t.o_se) : 0.0;
+                double gx, gy;
+                sample_grad(t, v_nw, v_ne, v_sw, v_se, gx, gy);
                 const double wc = ch == 0 ? wr : (ch == 1 ? wg : wb);
                 ax = ch == 0 ? wc * gx : ax + wc * gx;
                 ay = ch == 0 ? wc * gy : ay + wc * gy;
@@ -407,13 +288,7 @@ __global__ void __launch_bounds__(kThreads) flow_census_grad_kernel(CensusParams
     }
 }
 
-bool dims_ok(int32_t n, int32_t h, int32_t w) {
-    return n >= 1 && n <= 65535 && h >= 2 && w >= 2 && (int64_t)h * w < (1ll << 31);
-}
-
 bool patch_ok(int32_t patch) { return patch == 3 || patch == 5 || patch == 7; }
-
-bool aligned(const void* ptr, int a) { return ((uintptr_t)ptr % (uintptr_t)a) == 0; }
 
 int64_t tiles_of(int32_t extent, int tile) { return ((int64_t)extent + tile - 1) / tile; }
 
@@ -421,47 +296,25 @@ int64_t tiles_of(int32_t extent, int tile) { return ((int64_t)extent + tile - 1)
 int fill_operands(CensusParams* p, const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
                   const void* img, int64_t img_bs, const void* other, int64_t other_bs, int32_t channels, int32_t img_u8, float flow_sign,
                   int32_t patch, float thresh, float eps, float q, int32_t n, int32_t h, int32_t w) {
-    if (!dims_ok(n, h, w) || !patch_ok(patch)) return OFL_E_ARG;
-    if (flow_sign != 1.0f && flow_sign != -1.0f) return OFL_E_ARG;
+    if (!patch_ok(patch)) return OFL_E_ARG;
     if (channels != 1 && channels != 3) return OFL_E_ARG;
     if (!(thresh > 0.0f) || isinf(thresh) || !(eps > 0.0f) || isinf(eps) || !(q > 0.0f) || !(q <= 1.0f)) return OFL_E_ARG;  // (NaN fails)
-    if (flow == nullptr || img == nullptr || other == nullptr) return OFL_E_ARG;
-    if ((flow_half != 0 && flow_half != 1) || (img_u8 != 0 && img_u8 != 1)) return OFL_E_ARG;
-    if (flow_bs < 0 || mask_bs < 0 || img_bs < 0 || other_bs < 0) return OFL_E_ARG;
-    if (!aligned(flow, flow_half ? 2 : 4) || !aligned(img, img_u8 ? 1 : 4) || !aligned(other, img_u8 ? 1 : 4)) return OFL_E_ARG;
-    p->flow = flow; p->flow_bs = flow_bs;
-    p->mask = mask; p->mask_bs = mask_bs;
-    p->img = img; p->other = other; p->img_bs = img_bs; p->other_bs = other_bs;
-    p->hw = (int64_t)h * w;
-    p->chan = channels; p->h = h; p->w = w;
+    const int rc = fill_pair_operands(p, flow, flow_bs, flow_half, mask, mask_bs, img, img_bs, other, other_bs, channels, img_u8, flow_sign,
+                                      n, h, w);
+    if (rc) return rc;
     p->tiles_x = (int32_t)tiles_of(w, kTileW);
     p->nblk = (int32_t)(tiles_of(w, kTileW) * tiles_of(h, kTileH));        // (h * w < 2^31: under 2^27)
-    p->flow_sign = flow_sign; p->thresh = thresh; p->eps = eps; p->q = q;
-    p->wm1 = (float)(w - 1); p->hm1 = (float)(h - 1);
-    p->half_wm1 = p->wm1 / 2.0f; p->half_hm1 = p->hm1 / 2.0f;
-    p->partial = nullptr; p->map = nullptr; p->out = nullptr; p->scale = nullptr; p->grad = nullptr;
+    p->thresh = thresh; p->eps = eps; p->q = q;
     return OFL_OK;
 }
 
 template <int PATCH, bool BWD>
 void launch_patch(const CensusParams& p, bool half, bool u8, dim3 grid, hipStream_t s) {
-    if constexpr (BWD) {
-        if (half) {
-            if (u8) OFL_KLAUNCH((flow_census_grad_kernel<PATCH, true, true>), grid, dim3(kThreads), 0, s, p);
-            else OFL_KLAUNCH((flow_census_grad_kernel<PATCH, true, false>), grid, dim3(kThreads), 0, s, p);
-        } else {
-            if (u8) OFL_KLAUNCH((flow_census_grad_kernel<PATCH, false, true>), grid, dim3(kThreads), 0, s, p);
-            else OFL_KLAUNCH((flow_census_grad_kernel<PATCH, false, false>), grid, dim3(kThreads), 0, s, p);
-        }
-    } else {
-        if (half) {
-            if (u8) OFL_KLAUNCH((flow_census_kernel<PATCH, true, true>), grid, dim3(kThreads), 0, s, p);
-            else OFL_KLAUNCH((flow_census_kernel<PATCH, true, false>), grid, dim3(kThreads), 0, s, p);
-        } else {
-            if (u8) OFL_KLAUNCH((flow_census_kernel<PATCH, false, true>), grid, dim3(kThreads), 0, s, p);
-            else OFL_KLAUNCH((flow_census_kernel<PATCH, false, false>), grid, dim3(kThreads), 0, s, p);
-        }
-    }
+    dispatch_flags(half, u8, [&](auto HALF, auto U8) {
+        constexpr bool kHalf = decltype(HALF)::value, kU8 = decltype(U8)::value;
+        if constexpr (BWD) OFL_KLAUNCH((flow_census_grad_kernel<PATCH, kHalf, kU8>), grid, dim3(kThreads), 0, s, p);
+        else OFL_KLAUNCH((flow_census_kernel<PATCH, kHalf, kU8>), grid, dim3(kThreads), 0, s, p);
+    });
 }
 
 template <bool BWD>
@@ -476,7 +329,7 @@ void launch(const CensusParams& p, int patch, bool half, bool u8, dim3 grid, hip
 extern "C" {
 
 __attribute__((visibility("default"))) int64_t ofl_flow_census_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t patch) {
-    if (!dims_ok(n, h, w) || !patch_ok(patch)) return OFL_E_ARG;
+    if (!dims_ok(n, h, w, 2) || !patch_ok(patch)) return OFL_E_ARG;
     return (int64_t)n * tiles_of(w, kTileW) * tiles_of(h, kTileH) * kRec * (int64_t)sizeof(double);
 }
 

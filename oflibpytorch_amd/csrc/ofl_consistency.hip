@@ -9,37 +9,24 @@
 //   flow_consistency_finish_kernel   one block per image: the block records added in ascending block order
 //
 // The residual and `known` are the vectors and the mask of combine_with(mode 3) bit for bit; the composed flow is never written.  The
-// sample position, the tap weights and the four-term sums RESTATE unnormalise() and the body of warp_bwd_kernel of ofl_kernels.hip (the
-// generic backward warp: position unnormalise(grid - flow_sign * a), floorf, nw / ne / sw / se, `v_nw * nw` then three fmaf in the order
-// ne, sw, se, the same chain over the tap validities for mr; a tap outside the frame reads as 0, a tap that back's mask switches off
-// leaves mr only) -- a change there is made here too; tests/test_gpu_consistency.py compares the two on the device.
+// sample (position, taps, weights, the four-term sums) is the one of ofl_loss_common.hpp, which restates the backward warp of
+// ofl_kernels.hip; mr here runs the same chain over the tap validities (a tap that back's mask switches off leaves mr only);
+// tests/test_gpu_consistency.py compares the two on the device.
 //
 // One lane takes the 4 pixels 4 q .. 4 q + 3 of an image.  a's planes and mask and the outputs go through 16-byte / 4-byte accesses where
 // H*W, the batch strides and the pointers allow (chosen per launch), else one element at a time with bounds checks; the taps of `back`
-// are single loads straight from global memory in either form (element alignment is all `back` needs).  Sums as in ofl_metrics.hip:
-// blocks walk an image with a grid stride, their number depends on H*W only, a lane adds its pixels in ascending order, lanes by a
-// butterfly, waves and then blocks in index order: no float atomics, the record of an image carries the same bits in any batch and on
-// any run.  C ABI: include/oflib_hip.h.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "oflib_hip.h"
-
-#pragma clang fp contract(off)
-
-// the launch recorder of ofl_kernels.hip (ofl_last_kernel_name)
-extern const void* g_ofl_last_kernel;
-#define OFL_KLAUNCH(K, ...) do { g_ofl_last_kernel = (const void*)(K); hipLaunchKernelGGL(K, __VA_ARGS__); } while (0)
+// are single loads straight from global memory in either form (element alignment is all `back` needs).  Blocks walk an image with a grid
+// stride, their number depends on H*W only; the sums are those of ofl_loss_common.hpp.  C ABI: include/oflib_hip.h.
+#include "ofl_loss_common.hpp"
 
 namespace {
+
+using namespace ofl_loss;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxBlocks = 256;                    // blocks per image at most (one per CU); 1080p: each walks 7 or 8 steps of 1024 px
 constexpr int kRec = OFL_CONSISTENCY_RECORD;       // doubles per record
-constexpr float kValidThr = 0.99999f;              // ofl_kernels.hip (flow_class.py:922)
 // slots of a record (include/oflib_hip.h)
 enum { R_KNOWN = 0, R_CONS = 1, R_SUM = 2, R_MAX = 3, R_SUM_CONS = 4, R_USED = 5 };
 
@@ -58,19 +45,6 @@ struct ConsParams {
     double* out;                                   // [n][kRec]
 };
 
-// unnormalise() of ofl_kernels.hip: normalise_coords (utils.py:462-465) followed by the grid sampler's align_corners un-normalise
-__device__ __forceinline__ float unnormalise(float p, float size_m1, float half_size_m1) {
-    float g = p * 2.0f;
-    g = g / size_m1;  // IEEE correctly-rounded divide (no fast-math)
-    g = g - 1.0f;
-    return (g + 1.0f) * half_size_m1;
-}
-
-template <bool HALF>
-__device__ __forceinline__ float ld1(const void* base, int64_t i) {
-    return HALF ? __half2float(reinterpret_cast<const __half*>(base)[i]) : reinterpret_cast<const float*>(base)[i];
-}
-
 // four consecutive elements p0 .. p0 + 3 of one plane of `a` (`base` + o: its first element); VEC: all four exist and the access is aligned
 template <bool VEC, bool HALF>
 __device__ __forceinline__ void ld4(const void* base, int64_t o, int64_t p0, int64_t hw, float v[4]) {
@@ -85,7 +59,7 @@ __device__ __forceinline__ void ld4(const void* base, int64_t o, int64_t p0, int
         }
     } else {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = (p0 + k < hw) ? ld1<HALF>(base, o + p0 + k) : 0.0f;
+        for (int k = 0; k < 4; ++k) v[k] = (p0 + k < hw) ? ld_flow<HALF>(base, o + p0 + k) : 0.0f;
     }
 }
 
@@ -106,11 +80,9 @@ __device__ __forceinline__ uint32_t mask4(const uint8_t* mask, int64_t o, int64_
     return bits;
 }
 
-// correctly rounded fp32 square root (ofl_metrics.hip)
-__device__ __forceinline__ float sqrt_rn(float s) { return __builtin_sqrtf(s); }
-
 // the partner of pixel (x, y) whose vector is (u, v): `back` sampled at unnormalise(grid - flow_sign * a) and the weight sum of its valid
-// taps -- the body of warp_bwd_kernel (ofl_kernels.hip), two channels.  Taps are clamped into the plane: always addressable
+// taps, two channels.  The geometry is taps_of() of ofl_loss_common.hpp written out (through Taps the vector kernels take 111 to 122 VGPRs, not 102, by tools/isa_stats.py): a change
+// there is made here too.  Taps are clamped into the plane: always addressable
 template <bool HALF_B>
 __device__ __forceinline__ void partner(const ConsParams& p, const void* bb, const uint8_t* bm, int x, int y, float u, float v,
                                         float& bu, float& bv, float& mr) {
@@ -153,10 +125,10 @@ __device__ __forceinline__ void partner(const ConsParams& p, const void* bb, con
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         const int64_t pl = (int64_t)c * p.hw;
-        const float v_nw = k_nw ? ld1<HALF_B>(bb, pl + o_nw) : 0.0f;
-        const float v_ne = k_ne ? ld1<HALF_B>(bb, pl + o_ne) : 0.0f;
-        const float v_sw = k_sw ? ld1<HALF_B>(bb, pl + o_sw) : 0.0f;
-        const float v_se = k_se ? ld1<HALF_B>(bb, pl + o_se) : 0.0f;
+        const float v_nw = k_nw ? ld_flow<HALF_B>(bb, pl + o_nw) : 0.0f;
+        const float v_ne = k_ne ? ld_flow<HALF_B>(bb, pl + o_ne) : 0.0f;
+        const float v_sw = k_sw ? ld_flow<HALF_B>(bb, pl + o_sw) : 0.0f;
+        const float v_se = k_se ? ld_flow<HALF_B>(bb, pl + o_se) : 0.0f;
         float rr = v_nw * nw;
         rr = __builtin_fmaf(v_ne, ne, rr);
         rr = __builtin_fmaf(v_sw, sw, rr);
@@ -227,57 +199,17 @@ __global__ void __launch_bounds__(kThreads) flow_consistency_kernel(ConsParams p
         }
     }
     if (p.partial == nullptr) return;              // (the same for every thread of the launch)
-    // lanes: butterfly (every lane ends with the wave's value); waves: added in index order by the first threads
     double rec[kRec];
 #pragma unroll
     for (int i = 0; i < kRec; ++i) rec[i] = 0.0;
     rec[R_KNOWN] = (double)nknown; rec[R_CONS] = (double)ncons; rec[R_SUM] = sum; rec[R_MAX] = (double)mx; rec[R_SUM_CONS] = sum_cons;
-#pragma unroll
-    for (int i = 0; i < R_USED; ++i) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double o = __shfl_xor(rec[i], off);
-            rec[i] = (i == R_MAX) ? fmax(rec[i], o) : rec[i] + o;
-        }
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < kRec; ++i) s_red[wave * kRec + i] = rec[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < kRec) {
-        double s = s_red[threadIdx.x];
-        for (int wv = 1; wv < kWaves; ++wv) {
-            const double o = s_red[wv * kRec + threadIdx.x];
-            s = (threadIdx.x == R_MAX) ? fmax(s, o) : s + o;
-        }
-        p.partial[(img * p.nblk + blockIdx.x) * kRec + threadIdx.x] = s;
-    }
+    reduce_record<kRec, R_USED, R_MAX, kWaves>(rec, s_red, p.partial, img, p.nblk);
 }
 
-// one block per image: the block records staged in LDS by all threads (independent loads: summing straight from memory serialises up to
-// 256 load latencies per slot), then slot i added in ascending block order by thread i
+// one block per image: the block records added in ascending block order (all of them fit one chunk)
 __global__ void __launch_bounds__(kThreads) flow_consistency_finish_kernel(ConsParams p) {
-    __shared__ double s_part[kMaxBlocks * kRec];
-    const int64_t img = blockIdx.x;
-    const double* part = p.partial + img * p.nblk * kRec;
-    for (int i = threadIdx.x; i < p.nblk * kRec; i += kThreads) s_part[i] = part[i];
-    __syncthreads();
-    if (threadIdx.x >= kRec) return;
-    double s = 0.0;
-    for (int b = 0; b < p.nblk; ++b) {
-        const double o = s_part[b * kRec + threadIdx.x];
-        s = (threadIdx.x == R_MAX) ? fmax(s, o) : s + o;
-    }
-    p.out[img * kRec + threadIdx.x] = s;
+    finish_records<kRec, R_MAX, kMaxBlocks, kThreads>(p.partial, p.nblk, p.out);
 }
-
-bool dims_ok(int32_t n, int32_t h, int32_t w) {
-    return n >= 1 && n <= 65535 && h >= 2 && w >= 2 && (int64_t)h * w < (1ll << 31);
-}
-
-bool aligned(const void* ptr, int a) { return ((uintptr_t)ptr % (uintptr_t)a) == 0; }
 
 int64_t blocks_of(int64_t hw) {
     const int64_t b = ((hw + 3) / 4 + kThreads - 1) / kThreads;
@@ -293,13 +225,9 @@ bool vectorises(const ConsParams& p, bool a_half) {
 
 template <bool VEC>
 void launch(const ConsParams& p, bool a_half, bool b_half, dim3 grid, hipStream_t s) {
-    if (a_half) {
-        if (b_half) OFL_KLAUNCH((flow_consistency_kernel<VEC, true, true>), grid, dim3(kThreads), 0, s, p);
-        else OFL_KLAUNCH((flow_consistency_kernel<VEC, true, false>), grid, dim3(kThreads), 0, s, p);
-    } else {
-        if (b_half) OFL_KLAUNCH((flow_consistency_kernel<VEC, false, true>), grid, dim3(kThreads), 0, s, p);
-        else OFL_KLAUNCH((flow_consistency_kernel<VEC, false, false>), grid, dim3(kThreads), 0, s, p);
-    }
+    dispatch_flags(a_half, b_half, [&](auto HALF_A, auto HALF_B) {
+        OFL_KLAUNCH((flow_consistency_kernel<VEC, decltype(HALF_A)::value, decltype(HALF_B)::value>), grid, dim3(kThreads), 0, s, p);
+    });
 }
 
 }  // namespace
@@ -307,7 +235,7 @@ void launch(const ConsParams& p, bool a_half, bool b_half, dim3 grid, hipStream_
 extern "C" {
 
 __attribute__((visibility("default"))) int64_t ofl_flow_consistency_workspace_bytes(int32_t n, int32_t h, int32_t w) {
-    if (!dims_ok(n, h, w)) return OFL_E_ARG;
+    if (!dims_ok(n, h, w, 2)) return OFL_E_ARG;
     return (int64_t)n * blocks_of((int64_t)h * w) * kRec * (int64_t)sizeof(double);
 }
 
@@ -317,7 +245,7 @@ __attribute__((visibility("default"))) int ofl_flow_consistency_f32(const void* 
                                                                     float alpha, float beta, void* workspace, float* error,
                                                                     uint8_t* consistent, uint8_t* known, double* record,
                                                                     int32_t n, int32_t h, int32_t w, void* stream) {
-    if (!dims_ok(n, h, w)) return OFL_E_ARG;
+    if (!dims_ok(n, h, w, 2)) return OFL_E_ARG;
     if (flow_sign != 1.0f && flow_sign != -1.0f) return OFL_E_ARG;
     if (!(alpha >= 0.0f) || isinf(alpha) || !(beta >= 0.0f) || isinf(beta)) return OFL_E_ARG;      // (NaN fails the first test)
     if (!a || !back) return OFL_E_ARG;

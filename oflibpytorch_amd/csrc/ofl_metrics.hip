@@ -9,24 +9,13 @@
 //
 // One lane takes the 4 pixels 4 q .. 4 q + 3 of an image: 16-byte loads of the four vector planes (8 bytes of an fp16-stored flow) and
 // 4-byte loads of the masks where H*W, the batch strides and the pointers allow (chosen per launch), else one element at a time with
-// bounds checks.  Blocks walk an image with a grid stride; their number depends on H*W only, each lane adds its pixels in ascending
-// order, lanes are added by a butterfly, waves and then blocks in index order: no float atomics, the record of an image carries the
-// same bits in any batch and on any run.  Counts are integers until the record, where they are exact doubles.
-// C ABI: include/oflib_hip.h.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "oflib_hip.h"
-
-#pragma clang fp contract(off)
-
-// the launch recorder of ofl_kernels.hip (ofl_last_kernel_name)
-extern const void* g_ofl_last_kernel;
-#define OFL_KLAUNCH(K, ...) do { g_ofl_last_kernel = (const void*)(K); hipLaunchKernelGGL(K, __VA_ARGS__); } while (0)
+// bounds checks.  Blocks walk an image with a grid stride; their number depends on H*W only.  The sums are those of
+// ofl_loss_common.hpp; counts are integers until the record, where they are exact doubles.  C ABI: include/oflib_hip.h.
+#include "ofl_loss_common.hpp"
 
 namespace {
+
+using namespace ofl_loss;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -96,11 +85,6 @@ __device__ __forceinline__ uint32_t mask4(const uint8_t* mask, int64_t o, int64_
     return bits;
 }
 
-// correctly rounded fp32 square root: what hipcc makes of sqrtf by default (no fast-math, correctly rounded divide / sqrt left on).  The
-// float64 root rounded once is the same value by construction (53 >= 2 * 24 + 2 bits) and measured 15 % slower on the whole pass
-// (DESIGN.md 3.16); tests/test_gpu_flow_error.py holds this one to np.sqrt bit for bit, denormal sums of squares included
-__device__ __forceinline__ float sqrt_rn(float s) { return __builtin_sqrtf(s); }
-
 // the 4 pixels of lane `q`: the fp32 differences, the valid bits
 template <bool VEC>
 __device__ __forceinline__ uint32_t load_quad(const ErrParams& p, int64_t img, int64_t q, float du[4], float dv[4], float ug[4], float vg[4]) {
@@ -158,7 +142,6 @@ __global__ void __launch_bounds__(kThreads) flow_error_kernel(ErrParams p) {
             }
         }
     }
-    // lanes: butterfly (every lane ends with the wave's value); waves: added in index order by the first 16 threads
     double rec[kRec];
 #pragma unroll
     for (int i = 0; i < kRec; ++i) rec[i] = 0.0;
@@ -167,45 +150,12 @@ __global__ void __launch_bounds__(kThreads) flow_error_kernel(ErrParams p) {
     for (int t = 0; t < kMaxThr; ++t) rec[R_OVER + t] = (double)over[t];
 #pragma unroll
     for (int b = 0; b < 3; ++b) { rec[R_SPEED_COUNT + b] = (double)scnt[b]; rec[R_SPEED_SUM + b] = ssum[b]; }
-#pragma unroll
-    for (int i = 0; i < R_SPEED_SUM + 3; ++i) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double o = __shfl_xor(rec[i], off);
-            rec[i] = (i == R_MAX) ? fmax(rec[i], o) : rec[i] + o;
-        }
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < kRec; ++i) s_red[wave * kRec + i] = rec[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < kRec) {
-        double s = s_red[threadIdx.x];
-        for (int wv = 1; wv < kWaves; ++wv) {
-            const double o = s_red[wv * kRec + threadIdx.x];
-            s = (threadIdx.x == R_MAX) ? fmax(s, o) : s + o;
-        }
-        p.partial[(img * p.nblk + blockIdx.x) * kRec + threadIdx.x] = s;
-    }
+    reduce_record<kRec, R_SPEED_SUM + 3, R_MAX, kWaves>(rec, s_red, p.partial, img, p.nblk);
 }
 
-// one block per image: the block records staged in LDS by all threads (independent loads: summing straight from memory serialises up to
-// 256 load latencies per slot), then slot i added in ascending block order by thread i
+// one block per image: the block records added in ascending block order (all of them fit one chunk)
 __global__ void __launch_bounds__(kThreads) flow_error_finish_kernel(ErrParams p) {
-    __shared__ double s_part[kMaxBlocks * kRec];
-    const int64_t img = blockIdx.x;
-    const double* part = p.partial + img * p.nblk * kRec;
-    for (int i = threadIdx.x; i < p.nblk * kRec; i += kThreads) s_part[i] = part[i];
-    __syncthreads();
-    if (threadIdx.x >= kRec) return;
-    double s = 0.0;
-    for (int b = 0; b < p.nblk; ++b) {
-        const double o = s_part[b * kRec + threadIdx.x];
-        s = (threadIdx.x == R_MAX) ? fmax(s, o) : s + o;
-    }
-    p.out[img * kRec + threadIdx.x] = s;
+    finish_records<kRec, R_MAX, kMaxBlocks, kThreads>(p.partial, p.nblk, p.out);
 }
 
 // d mean(e) / d est = scale * (du, dv) / e: the float64 quotient of the fp32 differences, rounded once; 0 where not valid or e == 0
@@ -247,13 +197,7 @@ __global__ void __launch_bounds__(kThreads) flow_epe_grad_kernel(ErrParams p) {
     }
 }
 
-int dims_ok(int32_t n, int32_t h, int32_t w) {
-    if (n < 1 || h < 1 || w < 1 || n > 65535) return OFL_E_SHAPE;
-    if ((int64_t)h * w >= (1ll << 31)) return OFL_E_SHAPE;
-    return OFL_OK;
-}
-
-bool aligned(const void* ptr, int a) { return ((uintptr_t)ptr % (uintptr_t)a) == 0; }
+int shape_rc(int32_t n, int32_t h, int32_t w) { return dims_ok(n, h, w, 1) ? OFL_OK : OFL_E_SHAPE; }
 
 int64_t blocks_of(int64_t hw, int cap) {
     const int64_t b = ((hw + 3) / 4 + kThreads - 1) / kThreads;
@@ -290,7 +234,7 @@ bool inputs_vectorise(const ErrParams& p) {
 extern "C" {
 
 __attribute__((visibility("default"))) int64_t ofl_flow_error_workspace_bytes(int32_t n, int32_t h, int32_t w) {
-    const int rc = dims_ok(n, h, w);
+    const int rc = shape_rc(n, h, w);
     if (rc) return rc;
     return (int64_t)n * blocks_of((int64_t)h * w, kMaxBlocks) * kRec * (int64_t)sizeof(double);
 }
@@ -302,7 +246,7 @@ __attribute__((visibility("default"))) int ofl_flow_error_f64(const void* est, i
                                                               double* records,
                                                               int32_t n, int32_t h, int32_t w, void* stream) {
     if (!est || !gt || !workspace || !records) return OFL_E_NULL;
-    int rc = dims_ok(n, h, w);
+    int rc = shape_rc(n, h, w);
     if (rc) return rc;
     if (n_thresholds < 0 || n_thresholds > kMaxThr) return OFL_E_ARG;
     ErrParams p;
@@ -333,7 +277,7 @@ __attribute__((visibility("default"))) int ofl_flow_epe_grad_f32(const void* est
                                                                  float* grad_est, float* grad_gt, int32_t n, int32_t h, int32_t w,
                                                                  void* stream) {
     if (!est || !gt || !scale || (!grad_est && !grad_gt)) return OFL_E_NULL;
-    int rc = dims_ok(n, h, w);
+    int rc = shape_rc(n, h, w);
     if (rc) return rc;
     ErrParams p;
     rc = fill_operands(&p, est, est_bs, est_half, gt, gt_bs, gt_half, est_mask, est_mask_bs, gt_mask, gt_mask_bs, h, w);

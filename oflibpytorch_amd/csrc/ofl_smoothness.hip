@@ -14,23 +14,13 @@
 // 4 q .. 4 q + 3 of a row: 16-byte loads and stores (8 bytes of an fp16-stored flow, 4 of the mask or a uint8 image) where the width,
 // the batch strides and the pointers allow (chosen per launch, a uniform branch), else one element at a time with bounds checks -- the
 // same pixels in the same lanes, so the choice never changes a bit.  The validity byte is 0 outside the frame: a term whose taps are all
-// valid exists.  Blocks walk the tiles of an image with a grid stride; their number depends on (h, w) only, each lane adds its pixels in
-// ascending order, lanes are added by a butterfly, waves and then blocks in index order: no float atomics, the record of an image
-// carries the same bits in any batch and on any run.  C ABI: include/oflib_hip.h.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "oflib_hip.h"
-
-#pragma clang fp contract(off)
-
-// the launch recorder of ofl_kernels.hip (ofl_last_kernel_name)
-extern const void* g_ofl_last_kernel;
-#define OFL_KLAUNCH(K, ...) do { g_ofl_last_kernel = (const void*)(K); hipLaunchKernelGGL(K, __VA_ARGS__); } while (0)
+// valid exists.  Blocks walk the tiles of an image with a grid stride; their number depends on (h, w) only.  The sums are those of
+// ofl_loss_common.hpp.  C ABI: include/oflib_hip.h.
+#include "ofl_loss_common.hpp"
 
 namespace {
+
+using namespace ofl_loss;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -80,9 +70,6 @@ struct Tile {
     float img[IMG == IMG_NONE ? 1 : kMaxChan][IMG == IMG_NONE ? 4 : ROWS * kLW];
     uint8_t valid[ROWS * kLW];
 };
-
-// correctly rounded fp32 square root (ofl_metrics.hip)
-__device__ __forceinline__ float sqrt_rn(float s) { return __builtin_sqrtf(s); }
 
 enum { K_FLOAT = 0, K_HALF = 1, K_U8 = 2 };
 
@@ -321,56 +308,17 @@ __global__ void __launch_bounds__(kThreads) flow_smoothness_kernel(SmoothParams 
         __syncthreads();
     }
     if (BWD) return;
-    // lanes: butterfly (every lane ends with the wave's value); waves: added in index order by the first 8 threads
     double rec[kRec];
 #pragma unroll
     for (int i = 0; i < kRec; ++i) rec[i] = 0.0;
     rec[R_COUNT_X] = (double)cnt_x; rec[R_COUNT_Y] = (double)cnt_y; rec[R_SUM_X] = sum_x; rec[R_SUM_Y] = sum_y; rec[R_MAX] = (double)mx;
-#pragma unroll
-    for (int i = 0; i <= R_MAX; ++i) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double o = __shfl_xor(rec[i], off);
-            rec[i] = (i == R_MAX) ? fmax(rec[i], o) : rec[i] + o;
-        }
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < kRec; ++i) s_red[wave * kRec + i] = rec[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < kRec) {
-        double s = s_red[threadIdx.x];
-        for (int wv = 1; wv < kWaves; ++wv) {
-            const double o = s_red[wv * kRec + threadIdx.x];
-            s = (threadIdx.x == R_MAX) ? fmax(s, o) : s + o;
-        }
-        p.partial[(img * p.nblk + blockIdx.x) * kRec + threadIdx.x] = s;
-    }
+    reduce_record<kRec, R_MAX + 1, R_MAX, kWaves>(rec, s_red, p.partial, img, p.nblk);
 }
 
-// one block per image: the block records staged in LDS by all threads, then slot i added in ascending block order by thread i
+// one block per image: the block records added in ascending block order (all of them fit one chunk)
 __global__ void __launch_bounds__(kThreads) flow_smoothness_finish_kernel(SmoothParams p) {
-    __shared__ double s_part[kMaxBlocks * kRec];
-    const int64_t img = blockIdx.x;
-    const double* part = p.partial + img * p.nblk * kRec;
-    for (int i = threadIdx.x; i < p.nblk * kRec; i += kThreads) s_part[i] = part[i];
-    __syncthreads();
-    if (threadIdx.x >= kRec) return;
-    double s = 0.0;
-    for (int b = 0; b < p.nblk; ++b) {
-        const double o = s_part[b * kRec + threadIdx.x];
-        s = (threadIdx.x == R_MAX) ? fmax(s, o) : s + o;
-    }
-    p.out[img * kRec + threadIdx.x] = s;
+    finish_records<kRec, R_MAX, kMaxBlocks, kThreads>(p.partial, p.nblk, p.out);
 }
-
-bool dims_ok(int32_t n, int32_t h, int32_t w) {
-    return n >= 1 && h >= 1 && w >= 1 && n <= 65535 && (int64_t)h * w < (1ll << 31);
-}
-
-bool aligned(const void* ptr, int a) { return ((uintptr_t)ptr % (uintptr_t)a) == 0; }
 
 int64_t tiles_of(int32_t h, int32_t w) { return (int64_t)((h + kTH - 1) / kTH) * ((w + kTW - 1) / kTW); }
 
@@ -383,7 +331,7 @@ int64_t blocks_of(int32_t h, int32_t w, int cap) {
 int fill_operands(SmoothParams* p, const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
                   const void* img, int64_t img_bs, int32_t img_channels, int32_t img_u8, int32_t order, float alpha, float eps,
                   int32_t n, int32_t h, int32_t w) {
-    if (!dims_ok(n, h, w)) return OFL_E_ARG;
+    if (!dims_ok(n, h, w, 1)) return OFL_E_ARG;
     if (order != 1 && order != 2) return OFL_E_ARG;
     if (!(alpha >= 0.0f) || isinf(alpha) || !(eps >= 0.0f) || isinf(eps)) return OFL_E_ARG;      // (NaN fails the first test)
     if (flow == nullptr || (flow_half != 0 && flow_half != 1) || flow_bs < 0 || mask_bs < 0) return OFL_E_ARG;
@@ -422,7 +370,7 @@ void launch(const SmoothParams& p, int order, int kind, dim3 grid, hipStream_t s
 extern "C" {
 
 __attribute__((visibility("default"))) int64_t ofl_flow_smoothness_workspace_bytes(int32_t n, int32_t h, int32_t w) {
-    if (!dims_ok(n, h, w)) return OFL_E_ARG;
+    if (!dims_ok(n, h, w, 1)) return OFL_E_ARG;
     return (int64_t)n * blocks_of(h, w, kMaxBlocks) * kRec * (int64_t)sizeof(double);
 }
 
