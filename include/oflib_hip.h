@@ -1095,6 +1095,41 @@ int ofl_flow_ssim_grad_f32(const void* flow, int64_t flow_bs, int32_t flow_half,
                            int32_t window, float c1, float c2, const float* scale, float* grad, int32_t n, int32_t h, int32_t w,
                            void* stream);
 
+/*
+ * The local cost volume of a flow network (PWC-Net, LiteFlowNet, ARFlow, UFlow), warp and correlation in one pass (which
+ * defines the numbers; ofl_cost_volume.hip): Flow.cost_volume.  An extension: the reference has no such function.  `feat`: the features
+ * on the flow's own grid, `other`: those of the frame the flow points into, fp32 [*,C,h,w] with a batch stride in elements (0: one
+ * image for the whole batch), C >= 1; flow, flow_half, mask, flow_sign as for ofl_flow_photometric_f64.  radius R is 1 .. 4,
+ * D = (2 R + 1)^2.  Every step fp32 with one rounding per operation:
+ *   W_c(q), mr(q)  the sample of other_c where the flow points from q and the weight sum of its taps inside the frame, as in
+ *               ofl_flow_photometric_f64
+ *   usable(q)   q in the frame, valid in the mask, mr(q) > 0.99999f
+ *   W'_c(q)     usable(q) ? W_c(q) : +0  (selected: a pixel that is not usable loads no sample)
+ *   V[o](p)     = (sum over c ascending, from +0, of feat_c(p) * W'_c(p + o)) / float(C),  o = (dy + R) (2 R + 1) + dx + R, each product
+ *               rounded, then each sum: no fused multiply-add.  All C products are formed, against +0 too.
+ * Inputs are never written; the warped tensor is not written either.  No workspace.
+ *
+ * ofl_flow_cost_volume_f32: volume fp32 [n,D,h,w], every element WRITTEN.  One launch.
+ *
+ * ofl_flow_cost_volume_grad_f32: with the upstream gradient grad_volume fp32 [n,D,h,w] and gs = grad_volume / float(C),
+ *     grad_feat_c(p)   = sum over o ascending, from +0, of gs[o](p) * W'_c(p + o)                                      [n,C,h,w]
+ *     grad_warped_c(q) = usable(q) ? sum over o ascending, from +0, of gs[o](q - o) * feat_c(q - o), q - o in the frame : +0   [n,C,h,w]
+ *   both gathers: no scatter, no atomics, the same bits on any run.  Either output may be NULL, not both; every element of an output
+ *   given is written (a batch-broadcast feat still gets n gradient images: the caller adds them).  One launch per output.
+ *   grad_warped is the upstream gradient of the warp: ofl_warp_bwd_grad_f32 turns it into the gradients of `other` and of the flow.
+ *
+ * OFL_E_ARG, before any launch, for: n outside 1 .. 65535, h or w < 2, h * w >= 2^31, a flow_sign other than +-1, C < 1, a radius
+ * outside 1 .. 4, a NULL flow, feat, other, volume or grad_volume pointer, grad_feat and grad_warped both NULL, a negative stride, a
+ * flow_half that is neither 0 nor 1, a pointer not aligned to its element.
+ */
+int ofl_flow_cost_volume_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, const float* feat,
+                             int64_t feat_bs, const float* other, int64_t other_bs, int32_t channels, float flow_sign, int32_t radius,
+                             float* volume, int32_t n, int32_t h, int32_t w, void* stream);
+int ofl_flow_cost_volume_grad_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
+                                  const float* feat, int64_t feat_bs, const float* other, int64_t other_bs, int32_t channels,
+                                  float flow_sign, int32_t radius, const float* grad_volume, float* grad_feat, float* grad_warped,
+                                  int32_t n, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ implemented (`once_differentiable` raises).
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _census, _native, _photometric, _smoothness, _ssim
+from . import _census, _cost_volume, _native, _photometric, _smoothness, _ssim
 
 
 def _reduce_to(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
@@ -297,3 +297,36 @@ class CensusFn(_PairLossFn):
 class SsimFn(_PairLossFn):
     """ssim[n]: the SSIM penalty (Flow.ssim); params: flow_sign, window, c1, c2"""
     binding = (_ssim, "flow_ssim", "flow_ssim_grad")
+
+
+class CostVolumeFn(torch.autograd.Function):
+    """volume[n, o] = mean over the channels of feat(p) * W'(p + o), W' being `other` sampled where the flow points and +0 where the
+    pixel is not usable (Flow.cost_volume); params: flow_sign, radius.  Differentiable with respect to the vectors, `feat`
+    and `other`, not the mask: the gradient kernels give d feat and d W (gathers, bitwise reproducible), and the backward of the warp
+    (`_native.warp_bwd_grad`) turns d W into d other and d flow -- a call that is skipped when neither is needed.  The binding is looked
+    up by name at every call: the host tests replace `_cost_volume.flow_*` with fakes after this class exists."""
+
+    @staticmethod
+    def forward(ctx, vecs, mask, feat, other, flow_sign, radius):
+        vol = _cost_volume.flow_cost_volume(vecs.detach(), mask, feat.detach(), other.detach(), flow_sign, radius)
+        ctx.save_for_backward(vecs, mask, feat, other)
+        ctx.params = (flow_sign, radius)
+        return vol
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        vecs, mask, feat, other = ctx.saved_tensors
+        flow_sign, radius = ctx.params
+        need_flow, _, need_feat, need_other = ctx.needs_input_grad[:4]
+        need_warped = need_flow or need_other
+        g_feat, g_warped = _cost_volume.flow_cost_volume_grad(vecs.detach(), mask, feat.detach(), other.detach(), flow_sign, radius, g,
+                                                              want_feat=bool(need_feat), want_warped=bool(need_warped))
+        g_flow = g_other = None
+        if need_warped:
+            src = other.detach()
+            g_other, g_flow = _native.warp_bwd_grad(vecs.detach(), src[None] if src.dim() == 3 else src, g_warped, flow_sign=flow_sign,
+                                                    want_src=bool(need_other), want_flow=bool(need_flow))
+        like = lambda grad, t: _reduce_to(grad, t[None])[0] if t.dim() == 3 else _reduce_to(grad, t)      # C-H-W: summed over the batch
+        return (_reduce_to(g_flow, vecs) if need_flow else None, None, like(g_feat, feat) if need_feat else None,
+                like(g_other, other) if need_other else None, None, None)

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _census, _consistency, _native, _photometric, _smoothness, _ssim, distributed
+from . import _census, _consistency, _cost_volume, _native, _photometric, _smoothness, _ssim, distributed
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
@@ -1658,6 +1658,60 @@ class Flow(object):
         the SSIM term of an unsupervised flow loss.  The images carry no gradient, even if they require one; an element without a
         known pixel has gradient 0.  The backward pass gathers (no atomics): it is bitwise reproducible."""
         return _ssim.ssim(*self._ssim_operands(img, other, window, c1, c2, consider_mask)).to(self._device)
+
+    # ------------------------------------------------------------------------------------------
+    # cost volume (DESIGN.md 3.24; an extension: the reference has no such method)
+    # ------------------------------------------------------------------------------------------
+    def cost_volume(self, feat, other, radius: int = None, consider_mask: bool = None) -> torch.Tensor:
+        """The local cost volume of PWC-Net, LiteFlowNet, ARFlow and UFlow: the features `feat` on this flow's own grid correlated with
+        the features `other` of the frame the flow points into, warped by this flow, over a (2 `radius` + 1)^2 window.  `feat` and
+        `other` are float32 tensors or arrays, C-H-W (one image for the whole batch) or N-C-H-W, with the same C >= 1; `radius` is 1,
+        2, 3 or 4 (default 4: 81 offsets).  `other` is sampled bilinearly where the flow points, as :meth:`apply` does on a 't' flow;
+        a pixel is USABLE where it is valid in this flow's mask (with `consider_mask` False: everywhere) and its sample's taps lie in
+        the frame, and the warped value W' is the sample where the pixel is usable and 0 elsewhere and outside the frame (PWC-Net's
+        warp with its mask).  Returns float32 N-D-H-W on the flow's device, D = (2 `radius` + 1)^2: entry o = (dy + radius) (2 `radius`
+        + 1) + dx + radius at pixel p is the mean over the channels of feat(p) * W'(p + (dy, dx)).  One pass of ofl_cost_volume.hip
+        from LDS tiles: the warped tensor is never written, every sum runs in a fixed float32 order (bitwise reproducible, independent
+        of the batch), nothing is read back to the host.  Differentiable with respect to `feat`, `other` and the flow
+        vectors (not the mask); the gradients of `feat` and of the warped tensor are gathers without atomics.  Stride, dilation,
+        16-bit and channels_last features are not supported."""
+        err = "Error computing cost volume: "
+        feats = []
+        for name, ft in (("Feat", feat), ("Other", other)):
+            if isinstance(ft, np.ndarray):
+                if ft.dtype != np.float32:
+                    raise TypeError(err + name + " needs to be of dtype float32")
+                ft = torch.from_numpy(ft)
+            if not isinstance(ft, torch.Tensor):
+                raise TypeError(err + name + " needs to be a torch tensor or a numpy array")
+            if ft.dtype != torch.float32:
+                raise TypeError(err + name + " needs to be of dtype float32")
+            feats.append(ft)
+        for name, ft in zip(("Feat", "Other"), feats):
+            if ft.dim() not in (3, 4):
+                raise ValueError(err + name + " needs to have 3 or 4 dimensions, C-H-W or N-C-H-W")
+            if ft.shape[-3] < 1:
+                raise ValueError(err + name + " needs to have at least 1 channel")
+        if feats[0].shape[-3] != feats[1].shape[-3]:
+            raise ValueError(err + "Feat and other need to have the same number of channels")
+        for name, ft in zip(("Feat", "Other"), feats):
+            if tuple(ft.shape[-2:]) != tuple(self.shape[1:]):
+                raise ValueError(err + name + " needs to have the H-W shape of the flow")
+            if ft.dim() == 4 and ft.shape[0] != self.shape[0]:
+                raise ValueError(err + name + " needs to have the batch size of the flow")
+        if self.shape[1] < 2 or self.shape[2] < 2:
+            raise ValueError(err + "Flow field needs to be at least 2 pixels high and wide")
+        radius = _cost_volume.RADIUS if radius is None else radius
+        if not isinstance(radius, int) or isinstance(radius, bool):
+            raise TypeError(err + "Radius needs to be an integer")
+        if not 1 <= radius <= _cost_volume.MAX_RADIUS:
+            raise ValueError(err + "Radius needs to be 1, 2, 3 or 4")
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError(err + "Consider_mask needs to be boolean")
+        feats = [(ft if ft.device == self._device else ft.to(self._device)).contiguous() for ft in feats]      # (they keep their grad_fn)
+        return _cost_volume.cost_volume(self._fv, (self._mask if consider_mask else None), feats[0], feats[1],
+                                        -1.0 if self._ref == 's' else 1.0, radius).to(self._device)
 
     # ------------------------------------------------------------------------------------------
     # composition (flow_class.py:1648-1810)

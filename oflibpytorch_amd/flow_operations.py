@@ -164,6 +164,14 @@ def flow_ssim_stats(flow, img, other, ref: str, mask=None, window: int = None, c
     return stats if len(flow.shape) > 3 else {k: v.squeeze(0) for k, v in stats.items()}
 
 
+def flow_cost_volume(flow, feat, other, ref: str, mask=None, radius: int = None) -> torch.Tensor:
+    """Flow(flow, ref, mask).cost_volume(feat, other, radius): the local cost volume between the features `feat` on the flow's grid and
+    the features `other` of the frame it points into, float32 N-D-H-W with D = (2 radius + 1)^2 (D-H-W for 3-D input), differentiable
+    with respect to tensor `flow`, `feat` and `other`.  An extension: the reference has no such function."""
+    v = Flow(flow, ref, mask).cost_volume(feat, other, radius=radius)
+    return v if len(flow.shape) > 3 else v.squeeze(0)
+
+
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
     """Concatenate flow objects of equal H, W, ref and device along the batch axis (flow_operations.py:458-483)"""
     if not isinstance(flows, (list, tuple)):
