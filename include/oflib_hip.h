@@ -1129,6 +1129,23 @@ int ofl_flow_cost_volume_grad_f32(const void* flow, int64_t flow_bs, int32_t flo
                                   const float* feat, int64_t feat_bs, const float* other, int64_t other_bs, int32_t channels,
                                   float flow_sign, int32_t radius, const float* grad_volume, float* grad_feat, float* grad_warped,
                                   int32_t n, int32_t h, int32_t w, void* stream);
+/*
+ * The two per-pixel launches around ofl_warp_bwd_grad_f32 in the backward of the cost volume.  The rule: the gradient of the flow is +0
+ * wherever the pixel is not usable, and a value of `other` that no usable pixel samples reaches no gradient -- selected, not
+ * multiplied, as in the forward.
+ *
+ * ofl_flow_cost_volume_chain_f32: chain fp32 [n,2,h,w], every element WRITTEN: the flow's vectors as fp32, and (flow_sign * 2^31, 0)
+ *   where a component is not finite (that pixel is not usable and its grad_warped is +0; the vector puts its sample left of every
+ *   frame, so that no tap of it is read or written).  The backward of the warp is run on `chain`, not on the flow.
+ * ofl_flow_cost_volume_gate_f32: grad_flow fp32 [n,2,h,w], IN PLACE: +0 where usable(q) is false, untouched elsewhere.
+ *
+ * OFL_E_ARG, before any launch, for the frame, flow, flow_half, stride and flow_sign conditions above and a NULL or misaligned chain or
+ * grad_flow.
+ */
+int ofl_flow_cost_volume_chain_f32(const void* flow, int64_t flow_bs, int32_t flow_half, float flow_sign, float* chain, int32_t n,
+                                   int32_t h, int32_t w, void* stream);
+int ofl_flow_cost_volume_gate_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
+                                  float flow_sign, float* grad_flow, int32_t n, int32_t h, int32_t w, void* stream);
 
 #ifdef __cplusplus
 }

@@ -303,7 +303,8 @@ class CostVolumeFn(torch.autograd.Function):
     """volume[n, o] = mean over the channels of feat(p) * W'(p + o), W' being `other` sampled where the flow points and +0 where the
     pixel is not usable (Flow.cost_volume); params: flow_sign, radius.  Differentiable with respect to the vectors, `feat`
     and `other`, not the mask: the gradient kernels give d feat and d W (gathers, bitwise reproducible), and the backward of the warp
-    (`_native.warp_bwd_grad`) turns d W into d other and d flow -- a call that is skipped when neither is needed.  The binding is looked
+    (`_native.warp_bwd_grad`) turns d W into d other and d flow -- a call that is skipped when neither is needed; d flow is +0 wherever
+    the pixel is not usable (`flow_cost_volume_gate`), whatever `other` holds there.  The binding is looked
     up by name at every call: the host tests replace `_cost_volume.flow_*` with fakes after this class exists."""
 
     @staticmethod
@@ -324,9 +325,15 @@ class CostVolumeFn(torch.autograd.Function):
                                                               want_feat=bool(need_feat), want_warped=bool(need_warped))
         g_flow = g_other = None
         if need_warped:
+            # the rule of 3.24: d flow is +0 wherever the pixel is not usable, and a value of `other` that no usable pixel samples
+            # reaches no gradient.  The warp's backward knows nothing of `usable`: it runs on vectors that are finite everywhere
+            # (`chain`), and its d flow is gated by a kernel of the cost volume -- selected, not multiplied, as in the forward
             src = other.detach()
-            g_other, g_flow = _native.warp_bwd_grad(vecs.detach(), src[None] if src.dim() == 3 else src, g_warped, flow_sign=flow_sign,
+            chain = _cost_volume.flow_cost_volume_chain(vecs.detach(), flow_sign)
+            g_other, g_flow = _native.warp_bwd_grad(chain, src[None] if src.dim() == 3 else src, g_warped, flow_sign=flow_sign,
                                                     want_src=bool(need_other), want_flow=bool(need_flow))
+            if need_flow:
+                g_flow = _cost_volume.flow_cost_volume_gate(vecs.detach(), mask, flow_sign, g_flow)
         like = lambda grad, t: _reduce_to(grad, t[None])[0] if t.dim() == 3 else _reduce_to(grad, t)      # C-H-W: summed over the batch
         return (_reduce_to(g_flow, vecs) if need_flow else None, None, like(g_feat, feat) if need_feat else None,
                 like(g_other, other) if need_other else None, None, None)

@@ -1,6 +1,6 @@
 """ctypes binding of the fused cost volume (ofl_cost_volume.hip; C ABI: include/oflib_hip.h).
 
-A module of its own next to `_native`, whose helpers it uses: it declares the two entry points it calls and allocates its outputs under
+A module of its own next to `_native`, whose helpers it uses: it declares the four entry points it calls and allocates its outputs under
 its own module-level name `torch`, which the dirty-memory tests replace (tests/test_gpu_cost_volume_dirty_memory.py).
 """
 import ctypes
@@ -16,7 +16,7 @@ _declared = None
 
 
 def _library():
-    """libofl_hip.so with the two entry points of this module declared."""
+    """libofl_hip.so with the four entry points of this module declared."""
     global _declared
     lib = load_library()
     if _declared is not lib:
@@ -25,6 +25,10 @@ def _library():
         lib.ofl_flow_cost_volume_f32.restype = ctypes.c_int
         lib.ofl_flow_cost_volume_grad_f32.argtypes = [p, i64, i32, p, i64, p, i64, p, i64, i32, f32, i32, p, p, p, i32, i32, i32, p]
         lib.ofl_flow_cost_volume_grad_f32.restype = ctypes.c_int
+        lib.ofl_flow_cost_volume_chain_f32.argtypes = [p, i64, i32, f32, p, i32, i32, i32, p]
+        lib.ofl_flow_cost_volume_chain_f32.restype = ctypes.c_int
+        lib.ofl_flow_cost_volume_gate_f32.argtypes = [p, i64, i32, p, i64, f32, p, i32, i32, i32, p]
+        lib.ofl_flow_cost_volume_gate_f32.restype = ctypes.c_int
         _declared = lib
     return lib
 
@@ -83,6 +87,37 @@ def flow_cost_volume_grad(vecs: torch.Tensor, mask: torch.Tensor, feat: torch.Te
                                                  _stream(dev)), "ofl_flow_cost_volume_grad_f32")
     del keep
     return g_feat, g_warped
+
+
+def flow_cost_volume_chain(vecs: torch.Tensor, flow_sign: float) -> torch.Tensor:
+    """The vectors the backward of the warp is run on (ofl_flow_cost_volume_chain_f32): fp32 [N,2,H,W], the flow's own,
+    and a vector that points out of the frame where a component is not finite, so that such a pixel -- never usable, its gradient of W
+    +0 -- puts no NaN weight on that +0."""
+    lib, dev = _library(), device(vecs)
+    n, _, h, w = vecs.shape
+    with _on(dev):
+        v, vbs, half = _vis_flow(vecs, dev, n)
+        chain = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+        _check(lib.ofl_flow_cost_volume_chain_f32(_ptr(v), vbs, half, float(flow_sign), _ptr(chain), n, h, w, _stream(dev)),
+               "ofl_flow_cost_volume_chain_f32")
+    del v
+    return chain
+
+
+def flow_cost_volume_gate(vecs: torch.Tensor, mask: torch.Tensor, flow_sign: float, grad_flow: torch.Tensor) -> torch.Tensor:
+    """`grad_flow` fp32 [N,2,H,W] contiguous, in place: +0 where the pixel is not usable (ofl_flow_cost_volume_gate_f32) -- selected, not
+    multiplied, as in the forward.  Returns `grad_flow`; allocates nothing."""
+    lib, dev = _library(), device(vecs, mask, grad_flow)
+    n, _, h, w = vecs.shape
+    if grad_flow.dtype != torch.float32 or tuple(grad_flow.shape) != (n, 2, h, w) or not grad_flow.is_contiguous():
+        raise ValueError("oflibpytorch_amd: the gradient of the flow needs to be contiguous float32 of the flow's shape")
+    with _on(dev):
+        v, vbs, half = _vis_flow(vecs, dev, n)
+        m, mbs = (None, 0) if mask is None else _planes(mask, dev, torch.bool, n, "mask")
+        _check(lib.ofl_flow_cost_volume_gate_f32(_ptr(v), vbs, half, _ptr(m), mbs, float(flow_sign), _ptr(grad_flow), n, h, w,
+                                                 _stream(dev)), "ofl_flow_cost_volume_gate_f32")
+    del v, m
+    return grad_flow
 
 
 def cost_volume(vecs: torch.Tensor, mask: torch.Tensor, feat: torch.Tensor, other: torch.Tensor, flow_sign: float = -1.0,

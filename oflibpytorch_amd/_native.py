@@ -41,7 +41,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_flow_photometric_workspace_bytes", "ofl_flow_photometric_f64", "ofl_flow_photometric_grad_f32",  # (_photometric.py)
             "ofl_flow_census_workspace_bytes", "ofl_flow_census_f64", "ofl_flow_census_grad_f32",                 # (_census.py)
             "ofl_flow_ssim_workspace_bytes", "ofl_flow_ssim_f64", "ofl_flow_ssim_grad_f32",                       # (_ssim.py)
-            "ofl_flow_cost_volume_f32", "ofl_flow_cost_volume_grad_f32")                                          # (_cost_volume.py)
+            "ofl_flow_cost_volume_f32", "ofl_flow_cost_volume_grad_f32", "ofl_flow_cost_volume_chain_f32",       # (_cost_volume.py)
+            "ofl_flow_cost_volume_gate_f32")
 _lib = None
 _load_lock = threading.RLock()
 

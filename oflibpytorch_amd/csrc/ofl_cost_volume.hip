@@ -15,6 +15,14 @@
 //                                               and halo per chunk, and a lane walks the window once per channel (TO_W: back to front, so
 //                                               that o still ascends) into one sum per pixel.  No scatter, no atomics, no workspace
 //
+//   flow_cost_volume_chain_kernel<HALF>         the vectors the backward of the warp is run on (ofl_warp_bwd_grad_f32 / ofl_splat_sum_f32
+//                                               turn d W into d other and d flow): the flow's own as fp32, and a vector that points out of
+//                                               the frame where a component is not finite -- such a pixel is not usable, its d W is +0, and a
+//                                               NaN weight times that +0 must reach no gradient
+//   flow_cost_volume_gate_kernel<HALF>          d flow of that backward, in place: +0 where the pixel is not usable (selected, as in the
+//                                               forward: there d W is +0 and the warp's backward would form 0 * tap, NaN for a tap of `other`
+//                                               that is not finite and that no usable pixel samples)
+//
 // The warped tensor is never written.  The sample (position, taps, weights, the four-term sum and mr) is the one of ofl_loss_common.hpp.
 // Taps are single loads straight from global memory at offsets clamped into the plane: always addressable.
 //
@@ -230,32 +238,81 @@ __global__ void __launch_bounds__(kThreads) flow_cost_volume_grad_kernel(CvParam
     }
 }
 
+// the x component of the vector a pixel with a non-finite vector gets in the chain: flow_sign * 2^31 puts the sample at x - 2^31, left of
+// every legal frame (w < 2^31), so that no tap lies inside the frame
+constexpr float kChainAway = 2147483648.0f;
+
+template <bool HALF>
+__global__ void __launch_bounds__(kThreads) flow_cost_volume_chain_kernel(CvParams p) {
+    const int64_t n_img = blockIdx.y, fo = n_img * p.flow_bs;
+    float* out = p.grad + n_img * 2 * p.hw;
+    for (int64_t pix = (int64_t)blockIdx.x * kThreads + threadIdx.x; pix < p.hw; pix += (int64_t)gridDim.x * kThreads) {
+        float u = ld_flow<HALF>(p.flow, fo + pix), v = ld_flow<HALF>(p.flow, fo + p.hw + pix);
+        if (!(__builtin_isfinite(u) && __builtin_isfinite(v))) { u = p.flow_sign * kChainAway; v = 0.0f; }
+        out[pix] = u;
+        out[p.hw + pix] = v;
+    }
+}
+
+template <bool HALF>
+__global__ void __launch_bounds__(kThreads) flow_cost_volume_gate_kernel(CvParams p) {
+    const int64_t n_img = blockIdx.y;
+    float* gf = p.grad + n_img * 2 * p.hw;
+    for (int64_t pix = (int64_t)blockIdx.x * kThreads + threadIdx.x; pix < p.hw; pix += (int64_t)gridDim.x * kThreads) {
+        const int y = (int)(pix / p.w), x = (int)(pix - (int64_t)y * p.w);
+        Taps t;
+        if (!usable_of<HALF>(p, n_img, x, y, t)) {
+            gf[pix] = 0.0f;
+            gf[p.hw + pix] = 0.0f;
+        }
+    }
+}
+
 bool radius_ok(int32_t radius) { return radius >= 1 && radius <= kMaxRadius; }
 
 int64_t tiles_of(int32_t extent, int tile) { return ((int64_t)extent + tile - 1) / tile; }
 
-// the operands and the checks both entry points share
-int fill_operands(CvParams* p, const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, const float* feat,
-                  int64_t feat_bs, const float* other, int64_t other_bs, int32_t channels, float flow_sign, int32_t radius, int32_t n,
-                  int32_t h, int32_t w) {
+// the flow, its mask and the frame: the operands and the checks every entry point shares
+int fill_flow(CvParams* p, const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, float flow_sign,
+              int32_t n, int32_t h, int32_t w) {
     if (!dims_ok(n, h, w, 2)) return OFL_E_ARG;
-    if (!radius_ok(radius) || channels < 1) return OFL_E_ARG;
     if (flow_sign != 1.0f && flow_sign != -1.0f) return OFL_E_ARG;
-    if (flow == nullptr || feat == nullptr || other == nullptr) return OFL_E_ARG;
+    if (flow == nullptr) return OFL_E_ARG;
     if (flow_half != 0 && flow_half != 1) return OFL_E_ARG;
-    if (flow_bs < 0 || mask_bs < 0 || feat_bs < 0 || other_bs < 0) return OFL_E_ARG;
-    if (!aligned(flow, flow_half ? 2 : 4) || !aligned(feat, 4) || !aligned(other, 4)) return OFL_E_ARG;
+    if (flow_bs < 0 || mask_bs < 0) return OFL_E_ARG;
+    if (!aligned(flow, flow_half ? 2 : 4)) return OFL_E_ARG;
     p->flow = flow; p->flow_bs = flow_bs;
     p->mask = mask; p->mask_bs = mask_bs;
-    p->feat = feat; p->other = other; p->feat_bs = feat_bs; p->other_bs = other_bs;
+    p->feat = nullptr; p->other = nullptr; p->feat_bs = 0; p->other_bs = 0;
     p->hw = (int64_t)h * w;
-    p->chan = channels; p->h = h; p->w = w;
+    p->chan = 0; p->h = h; p->w = w;
     p->tiles_x = (int32_t)tiles_of(w, kTileW);
     p->flow_sign = flow_sign;
     p->wm1 = (float)(w - 1); p->hm1 = (float)(h - 1);
     p->half_wm1 = p->wm1 / 2.0f; p->half_hm1 = p->hm1 / 2.0f;
     p->out = nullptr; p->g = nullptr; p->grad = nullptr;
     return OFL_OK;
+}
+
+// the operands and the checks the volume and its gradients share
+int fill_operands(CvParams* p, const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, const float* feat,
+                  int64_t feat_bs, const float* other, int64_t other_bs, int32_t channels, float flow_sign, int32_t radius, int32_t n,
+                  int32_t h, int32_t w) {
+    const int rc = fill_flow(p, flow, flow_bs, flow_half, mask, mask_bs, flow_sign, n, h, w);
+    if (rc) return rc;
+    if (!radius_ok(radius) || channels < 1) return OFL_E_ARG;
+    if (feat == nullptr || other == nullptr) return OFL_E_ARG;
+    if (feat_bs < 0 || other_bs < 0) return OFL_E_ARG;
+    if (!aligned(feat, 4) || !aligned(other, 4)) return OFL_E_ARG;
+    p->feat = feat; p->other = other; p->feat_bs = feat_bs; p->other_bs = other_bs;
+    p->chan = channels;
+    return OFL_OK;
+}
+
+// the grid of the two per-pixel kernels: 256 pixels per block, grid-stride beyond the cap
+dim3 pixel_grid_of(int32_t n, int32_t h, int32_t w) {
+    const int64_t blocks = ((int64_t)h * w + kThreads - 1) / kThreads;
+    return dim3((unsigned)(blocks < 65536 ? blocks : 65536), (unsigned)n);
 }
 
 dim3 grid_of(int32_t n, int32_t h, int32_t w) {
@@ -324,6 +381,33 @@ __attribute__((visibility("default"))) int ofl_flow_cost_volume_grad_f32(const v
                         dim3(kThreads), 0, s, p);
         });
     }
+    return (int)hipGetLastError();
+}
+
+__attribute__((visibility("default"))) int ofl_flow_cost_volume_chain_f32(const void* flow, int64_t flow_bs, int32_t flow_half, float flow_sign,
+                                                                          float* chain, int32_t n, int32_t h, int32_t w, void* stream) {
+    CvParams p;
+    const int rc = fill_flow(&p, flow, flow_bs, flow_half, nullptr, 0, flow_sign, n, h, w);
+    if (rc) return rc;
+    if (!chain || !aligned(chain, 4)) return OFL_E_ARG;
+    p.grad = chain;
+    hipStream_t s = (hipStream_t)stream;
+    if (flow_half) OFL_KLAUNCH((flow_cost_volume_chain_kernel<true>), pixel_grid_of(n, h, w), dim3(kThreads), 0, s, p);
+    else OFL_KLAUNCH((flow_cost_volume_chain_kernel<false>), pixel_grid_of(n, h, w), dim3(kThreads), 0, s, p);
+    return (int)hipGetLastError();
+}
+
+__attribute__((visibility("default"))) int ofl_flow_cost_volume_gate_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask,
+                                                                         int64_t mask_bs, float flow_sign, float* grad_flow, int32_t n,
+                                                                         int32_t h, int32_t w, void* stream) {
+    CvParams p;
+    const int rc = fill_flow(&p, flow, flow_bs, flow_half, mask, mask_bs, flow_sign, n, h, w);
+    if (rc) return rc;
+    if (!grad_flow || !aligned(grad_flow, 4)) return OFL_E_ARG;
+    p.grad = grad_flow;
+    hipStream_t s = (hipStream_t)stream;
+    if (flow_half) OFL_KLAUNCH((flow_cost_volume_gate_kernel<true>), pixel_grid_of(n, h, w), dim3(kThreads), 0, s, p);
+    else OFL_KLAUNCH((flow_cost_volume_gate_kernel<false>), pixel_grid_of(n, h, w), dim3(kThreads), 0, s, p);
     return (int)hipGetLastError();
 }
 

@@ -218,6 +218,34 @@ def fake_flow_cost_volume(vecs, mask, feat, other, flow_sign=-1.0, radius=RADIUS
     return torch.from_numpy(res['volume'])
 
 
+CHAIN_AWAY = F32(2.0 ** 31)
+
+
+def chain_vectors(a, ref):
+    """float32 [N,2,H,W]: the vectors the backward of the warp is run on -- the flow's own, and (sign * 2^31, 0) where a component is
+    not finite"""
+    f = np.asarray(a).astype(F32)
+    bad = ~np.isfinite(f).all(1)
+    f[:, 0][bad], f[:, 1][bad] = F32(sign_of(ref)) * CHAIN_AWAY, F32(0.0)
+    return f
+
+
+def usable_of(a, mask, ref):
+    """bool [N,H,W]: `usable` of the definition, which no value of `other` enters"""
+    f = po._as_f32(a)
+    return warped(f, mask, np.zeros((f.shape[0], 1) + f.shape[2:], F32), ref)[1]
+
+
+def fake_flow_cost_volume_chain(vecs, flow_sign):
+    return torch.from_numpy(chain_vectors(vecs.detach().numpy(), 's' if flow_sign < 0 else 't'))
+
+
+def fake_flow_cost_volume_gate(vecs, mask, flow_sign, grad_flow):
+    usable = usable_of(vecs.detach().numpy(), None if mask is None else mask.numpy(), 's' if flow_sign < 0 else 't')
+    grad_flow[torch.from_numpy(~np.broadcast_to(usable[:, None], tuple(grad_flow.shape)))] = 0.0
+    return grad_flow
+
+
 def fake_flow_cost_volume_grad(vecs, mask, feat, other, flow_sign, radius, grad_volume, want_feat=True, want_warped=True):
     d_feat, d_w = grads(vecs.detach().numpy(), None if mask is None else mask.numpy(), feat.detach().numpy(), other.detach().numpy(),
                         's' if flow_sign < 0 else 't', radius, grad_volume.detach().numpy())

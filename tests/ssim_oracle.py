@@ -219,3 +219,16 @@ def fake_flow_ssim(vecs, mask, img, other, flow_sign=-1.0, window=WINDOW, c1=C1,
     res = compute(vecs.detach().numpy(), None if mask is None else mask.numpy(), img.numpy(), other.numpy(),
                   's' if flow_sign < 0 else 't', window, c1, c2)
     return (torch.from_numpy(res['records']) if want_record else None), (torch.from_numpy(res['map']) if want_map else None)
+
+
+def fake_flow_ssim_grad_for(upstream):
+    """A stand-in for `_ssim.flow_ssim_grad` that answers with the oracle's float64 gradient for the upstream gradient `upstream`, rounded
+    to float32; it checks that the scale it is handed is that upstream over the count"""
+    def fake(vecs, mask, img, other, flow_sign, window, c1, c2, scale):
+        ref = 's' if flow_sign < 0 else 't'
+        args = (vecs.detach().numpy(), None if mask is None else mask.numpy(), img.numpy(), other.numpy(), ref, window, c1, c2)
+        res = compute(*args)
+        with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+            assert np.array_equal(scale.numpy(), (np.asarray(upstream, F32).astype(F64) / res['records'][:, 0]).astype(F32), equal_nan=True)
+            return torch.from_numpy(grad(*args, upstream=upstream, res=res)[0].astype(F32))
+    return fake

@@ -23,6 +23,8 @@ def cv_native(oracle_native, monkeypatch):
     from oflibpytorch_amd import _cost_volume
     monkeypatch.setattr(_cost_volume, "flow_cost_volume", cv.fake_flow_cost_volume)
     monkeypatch.setattr(_cost_volume, "flow_cost_volume_grad", cv.fake_flow_cost_volume_grad)
+    monkeypatch.setattr(_cost_volume, "flow_cost_volume_chain", cv.fake_flow_cost_volume_chain)
+    monkeypatch.setattr(_cost_volume, "flow_cost_volume_gate", cv.fake_flow_cost_volume_gate)
     return _cost_volume
 
 
@@ -325,7 +327,7 @@ def test_the_method_and_adapter_are_exported():
 # ---- the C ABI: declared, exported, and every rejected argument is rejected before any launch --------------------------------------
 def test_c_abi_declarations_and_argument_checks_need_no_gpu():
     from oflibpytorch_amd import _cost_volume, _native
-    names = {"ofl_flow_cost_volume_f32", "ofl_flow_cost_volume_grad_f32"}
+    names = {"ofl_flow_cost_volume_f32", "ofl_flow_cost_volume_grad_f32", "ofl_flow_cost_volume_chain_f32", "ofl_flow_cost_volume_gate_f32"}
     assert names <= set(_native.exported_symbols())
     header = open(_native._build.HEADERS[0]).read()
     for name in names:
@@ -357,3 +359,15 @@ def test_c_abi_declarations_and_argument_checks_need_no_gpu():
         assert fwd(**kw) == -3, kw
     for kw in shared + (dict(g=null), dict(g=odd), dict(d_feat=null, d_w=null), dict(d_feat=odd), dict(d_w=odd)):
         assert bwd(**kw) == -3, kw
+
+    def chain(flow=one, flow_bs=0, half=0, sign=-1.0, out=one, n=1, h=4, w=4):
+        return lib.ofl_flow_cost_volume_chain_f32(flow, flow_bs, half, sign, out, n, h, w, null)
+
+    def gate(flow=one, flow_bs=0, half=0, mask=null, mask_bs=0, sign=-1.0, out=one, n=1, h=4, w=4):
+        return lib.ofl_flow_cost_volume_gate_f32(flow, flow_bs, half, mask, mask_bs, sign, out, n, h, w, null)
+    flow_only = (dict(n=0), dict(n=65536), dict(h=1), dict(w=1), dict(h=46341, w=46341), dict(sign=0.0), dict(sign=nan), dict(flow=null),
+                 dict(flow_bs=-1), dict(half=2), dict(flow=odd), dict(out=null), dict(out=odd))
+    for kw in flow_only:
+        assert chain(**kw) == -3, kw
+    for kw in flow_only + (dict(mask_bs=-32),):
+        assert gate(**kw) == -3, kw

@@ -2,7 +2,8 @@
 
 `_cost_volume` allocates its outputs with `torch.empty` under its own module-level name `torch`; here that name is a
 `dirty_memory.Harness` proxy, so every such tensor is carved out of a buffer  guard | body | guard  whose body holds the fill byte.  For
-the volume and for both gradient kernels: the same bits under the fills 0x00, 0xFF and 0x55 (nothing stale is read, every element of
+the volume, for both gradient kernels and for the two per-pixel kernels of the backward (the chain vectors, a buffer of their own, and
+the select of d flow, which works in place and allocates nothing): the same bits under the fills 0x00, 0xFF and 0x55 (nothing stale is read, every element of
 every output is written), no guard of any allocation is written, the inputs -- guarded copies, their guards holding the fill byte -- are
 unchanged, and every allocation is made by a function of the new module.  The kernels have no workspace."""
 import numpy as np
@@ -36,9 +37,20 @@ def _run(fill, n, h, w, ref, what, half, radius, c):
         elif what == "grads":
             res = list(_cost_volume.flow_cost_volume_grad(a, m, feat, other, cv.sign_of(ref), radius, g))
             allocations, callers = 2, ["flow_cost_volume_grad"]
-        else:
+        elif what == "grad-warped":
             res = [_cost_volume.flow_cost_volume_grad(a, m, feat, other, cv.sign_of(ref), radius, g, want_feat=False)[1]]
             allocations, callers = 1, ["flow_cost_volume_grad"]
+        elif what == "chain":
+            res = [_cost_volume.flow_cost_volume_chain(a, cv.sign_of(ref))]
+            allocations, callers = 1, ["flow_cost_volume_chain"]
+        else:
+            # the select of d flow works in place on a gradient it is handed and allocates nothing: the gradient is a guarded
+            # allocation of this function, filled with finite values
+            gf = harness.proxy.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+            gf.copy_(torch.from_numpy(cv.upstream(n, 2, h, w).copy()))
+            res = [_cost_volume.flow_cost_volume_gate(a, m, cv.sign_of(ref), gf)]
+            assert res[0] is gf
+            allocations, callers = 1, ["_run"]
         torch.cuda.synchronize()
     finally:
         _cost_volume.torch = torch
@@ -50,7 +62,7 @@ def _run(fill, n, h, w, ref, what, half, radius, c):
 
 
 @pytest.mark.parametrize("half,radius,c", [(False, 4, 17), (True, 1, 3)], ids=["fp32-radius4", "fp16-radius1"])
-@pytest.mark.parametrize("what", ["volume", "grads", "grad-warped"])
+@pytest.mark.parametrize("what", ["volume", "grads", "grad-warped", "chain", "gate"])
 @pytest.mark.parametrize("ref", cv.REFS)
 @pytest.mark.parametrize("n,h,w", FRAMES)
 def test_same_bits_under_every_fill(n, h, w, ref, what, half, radius, c):
@@ -62,6 +74,13 @@ def test_same_bits_under_every_fill(n, h, w, ref, what, half, radius, c):
         feat, other = cv.features(n, c, h, w, ref)
         if what == "volume":
             want = [cv.compute(a, m, feat, other, ref, radius)['volume']]
+        elif what == "chain":
+            want = [cv.chain_vectors(a, ref)]
+            assert np.array_equal(want[0], a)                                # (finite vectors: the flow's own)
+        elif what == "gate":
+            usable = cv.usable_of(a, m, ref)
+            want = [np.where(usable[:, None], cv.upstream(n, 2, h, w), np.float32(0.0)).astype(np.float32)]
+            assert 0.1 < usable.mean() < 0.9
         else:
             want = list(cv.grads(a, m, feat, other, ref, radius, cv.upstream(n, (2 * radius + 1) ** 2, h, w)))[-len(results[0]):]
         for got, exp in zip(results[0], want):
