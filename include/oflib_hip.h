@@ -1147,6 +1147,68 @@ int ofl_flow_cost_volume_chain_f32(const void* flow, int64_t flow_bs, int32_t fl
 int ofl_flow_cost_volume_gate_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
                                   float flow_sign, float* grad_flow, int32_t n, int32_t h, int32_t w, void* stream);
 
+/*
+ * The correlation lookup of RAFT-style networks (RAFT, GMA, SEA-RAFT, CRAFT), computed on the fly at the looked-up positions without
+ * the all-pairs volume (which defines the numbers; ofl_corr_lookup.hip): Flow.corr_lookup.  An extension: the reference
+ * has no such function.  One call serves ONE pyramid level l = `level`, 0 .. 5: `other` is that level, fp32 [*,C,level_h,level_w] with a
+ * batch stride in elements (0: one image for the whole batch), level_h and level_w 1 .. 2^24 with level_h * level_w < 2^31; `feat`: the
+ * features on the flow's own grid, fp32 [*,C,h,w]; flow, flow_half, mask, flow_sign as for ofl_flow_photometric_f64, but h and w may
+ * be 1.  radius R is 1 .. 4, D = (2 R + 1)^2.  Every step fp32 with one rounding per operation:
+ *   usable(p)   valid in the mask and both vector components finite
+ *   position    px = float(x) - flow_sign * u, sx = px * 2^-l, x_w = floorf(sx), ww = sx - x_w, e = 1 - ww; py, sy, y_n, nn, s alike;
+ *               nw = s * e, ne = s * ww, sw = nn * e, se = nn * ww
+ *   node (j,i)  j, i = 0 .. 2 R + 1: column cx = x_w + float(i - R), row cy = y_n + float(j - R) of the level; inside where
+ *               cx > -1 && cx < level_w && cy > -1 && cy < level_h (float compares)
+ *   K[j,i]      = sum over c ascending, from +0, of feat_c(p) * other[c, cy, cx], each product rounded, then each sum; +0 (selected)
+ *               for a node outside
+ *   entry (dx + R) (2 R + 1) + dy + R, dx, dy = -R .. R  (the x offset is the outer index: RAFT's order)
+ *               = (K[dy+R, dx+R] * nw, then fmaf of K[dy+R, dx+R+1] with ne, K[dy+R+1, dx+R] with sw, K[dy+R+1, dx+R+1] with se)
+ *                 / sqrtf(float(C)); +0 (selected) for all D entries where usable(p) is false.
+ * Inputs are never written.
+ *
+ * ofl_flow_corr_lookup_f32: the D planes of the level into `out`, fp32 [n][D][h w] with `out_bs` >= D h w elements between images (the
+ *   level's channel slice of a result [n, L D, h, w]); every element of the D planes WRITTEN.  One launch.
+ *
+ * The backward of a level, with the level's slice `grad_out` of the upstream gradient (laid out as `out`, stride grad_bs) and
+ * gs = grad_out / sqrtf(float(C)):
+ * ofl_flow_corr_lookup_nodes_f32: nodes fp32 [n][(2 R + 2)^2][h w], every element WRITTEN:
+ *     Gn[j,i](p) = from +0, the terms that exist in this order, each product rounded, then added: gs[(i-R, j-R)] * nw  (j, i <= 2 R),
+ *                  gs[(i-1-R, j-R)] * ne  (j <= 2 R, i >= 1),  gs[(i-R, j-1-R)] * sw  (j >= 1, i <= 2 R),  gs[(i-1-R, j-1-R)] * se
+ *                  (j, i >= 1); +0 where usable(p) is false.
+ *   keys (NULL: not made) int64 [n][h w], every element WRITTEN: (image * cells + cell(p)) * h w + p, where cells =
+ *   ofl_flow_corr_lookup_cells(level_h, level_w, R) = (level_h + 2 R + 1) (level_w + 2 R + 1) + 1 and cell(p) =
+ *   (y_n - R + 2 R + 1) (level_w + 2 R + 1) + (x_w - R + 2 R + 1), the window's first node on the level's grid padded to the north and
+ *   west; the sentinel cells - 1 where usable(p) is false or no node of the window is inside.  The keys are unique.
+ * ofl_flow_corr_lookup_grad_feat_f32: grad_feat fp32 [n,C,h,w], every element WRITTEN:
+ *     grad_feat_c(p) = (accumulate ? the stored value : +0) + sum over j, then i ascending of Gn[j,i](p) * other[c, node], nodes outside
+ *     skipped; +0 where usable(p) is false.  Levels run as ascending calls, accumulate 0 for the first: one running sum.
+ * ofl_flow_corr_lookup_grad_other_f32: grad_other fp32 [n,C,level_h,level_w], every element WRITTEN, a gather without atomics:
+ *     grad_other[c,q] = from +0, over j, then i, then the pixels p of cell q - (j, i) in ascending order: + Gn[j,i](p) * feat_c(p)
+ *   `order` int64 [n h w]: the pixel index image * h w + p of every key in ascending key order; `starts` int64 [n cells + 1]: the
+ *   number of keys below k h w, k = 0 .. n cells.  Entries of `order` outside the image and runs outside [0, n h w] are skipped.
+ *
+ * OFL_E_ARG, before any launch, for: n outside 1 .. 65535, h or w < 1, h * w >= 2^31, C < 1 (the gather: C > 524280), a radius outside
+ * 1 .. 4, a level outside 0 .. 5, a level_h or level_w outside 1 .. 2^24 or level_h * level_w >= 2^31, n * cells * h * w >= 4e18, a
+ * flow_sign other than +-1, a NULL required pointer, a negative stride, out_bs or grad_bs < D h w, a flow_half or accumulate that is
+ * neither 0 nor 1, a pointer not aligned to its element.  ofl_flow_corr_lookup_cells returns OFL_E_ARG for a level or radius so refused.
+ */
+int64_t ofl_flow_corr_lookup_cells(int32_t level_h, int32_t level_w, int32_t radius);
+int ofl_flow_corr_lookup_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, const float* feat,
+                             int64_t feat_bs, const float* other, int64_t other_bs, int32_t channels, float flow_sign, int32_t radius,
+                             int32_t level, int32_t level_h, int32_t level_w, float* out, int64_t out_bs, int32_t n, int32_t h, int32_t w,
+                             void* stream);
+int ofl_flow_corr_lookup_nodes_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
+                                   int32_t channels, float flow_sign, int32_t radius, int32_t level, int32_t level_h, int32_t level_w,
+                                   const float* grad_out, int64_t grad_bs, float* nodes, int64_t* keys, int32_t n, int32_t h, int32_t w,
+                                   void* stream);
+int ofl_flow_corr_lookup_grad_feat_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
+                                       const float* other, int64_t other_bs, int32_t channels, float flow_sign, int32_t radius,
+                                       int32_t level, int32_t level_h, int32_t level_w, const float* nodes, float* grad_feat,
+                                       int32_t accumulate, int32_t n, int32_t h, int32_t w, void* stream);
+int ofl_flow_corr_lookup_grad_other_f32(const float* feat, int64_t feat_bs, int32_t channels, int32_t radius, int32_t level_h,
+                                        int32_t level_w, const float* nodes, const int64_t* order, const int64_t* starts,
+                                        float* grad_other, int32_t n, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ implemented (`once_differentiable` raises).
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _census, _cost_volume, _native, _photometric, _smoothness, _ssim
+from . import _census, _corr_lookup, _cost_volume, _native, _photometric, _smoothness, _ssim
 
 
 def _reduce_to(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
@@ -337,3 +337,31 @@ class CostVolumeFn(torch.autograd.Function):
         like = lambda grad, t: _reduce_to(grad, t[None])[0] if t.dim() == 3 else _reduce_to(grad, t)      # C-H-W: summed over the batch
         return (_reduce_to(g_flow, vecs) if need_flow else None, None, like(g_feat, feat) if need_feat else None,
                 like(g_other, other) if need_other else None, None, None)
+
+
+class CorrLookupFn(torch.autograd.Function):
+    """lookup[n, l D + (dx + r)(2 r + 1) + dy + r] = the bilinear sample, at (p + flow(p)) / 2^l + (dx, dy), of the correlation of feat(p)
+    with level l, over sqrt(C) (Flow.corr_lookup); params: flow_sign, radius; the levels follow as further arguments.
+    Differentiable with respect to `feat` and every level, not the vectors or the mask (RAFT detaches the coordinates before every
+    lookup): both gradients are gathers in a fixed order, bitwise reproducible.  The binding is looked up by name at every call: the
+    host tests replace `_corr_lookup.flow_*` with fakes after this class exists."""
+
+    @staticmethod
+    def forward(ctx, vecs, mask, feat, flow_sign, radius, *levels):
+        out = _corr_lookup.flow_corr_lookup(vecs.detach(), mask, feat.detach(), [lv.detach() for lv in levels], flow_sign, radius)
+        ctx.save_for_backward(vecs, mask, feat, *levels)
+        ctx.params = (flow_sign, radius)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        vecs, mask, feat = ctx.saved_tensors[:3]
+        levels = ctx.saved_tensors[3:]
+        flow_sign, radius = ctx.params
+        need_feat, need_levels = ctx.needs_input_grad[2], ctx.needs_input_grad[5:]
+        g_feat, g_levels = _corr_lookup.flow_corr_lookup_grad(vecs.detach(), mask, feat.detach(), [lv.detach() for lv in levels], flow_sign,
+                                                              radius, g, want_feat=bool(need_feat), want_levels=need_levels)
+        like = lambda grad, t: _reduce_to(grad, t[None])[0] if t.dim() == 3 else _reduce_to(grad, t)      # C-H-W: summed over the batch
+        return (None, None, like(g_feat, feat) if need_feat else None, None, None) + tuple(
+            like(gl, lv) if need else None for gl, lv, need in zip(g_levels, levels, need_levels))

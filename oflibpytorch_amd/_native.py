@@ -42,7 +42,9 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_flow_census_workspace_bytes", "ofl_flow_census_f64", "ofl_flow_census_grad_f32",                 # (_census.py)
             "ofl_flow_ssim_workspace_bytes", "ofl_flow_ssim_f64", "ofl_flow_ssim_grad_f32",                       # (_ssim.py)
             "ofl_flow_cost_volume_f32", "ofl_flow_cost_volume_grad_f32", "ofl_flow_cost_volume_chain_f32",       # (_cost_volume.py)
-            "ofl_flow_cost_volume_gate_f32")
+            "ofl_flow_cost_volume_gate_f32",
+            "ofl_flow_corr_lookup_cells", "ofl_flow_corr_lookup_f32", "ofl_flow_corr_lookup_nodes_f32",          # (_corr_lookup.py)
+            "ofl_flow_corr_lookup_grad_feat_f32", "ofl_flow_corr_lookup_grad_other_f32")
 _lib = None
 _load_lock = threading.RLock()
 
@@ -165,6 +167,7 @@ def _load_library_locked(path: str = None):
     lib.ofl_last_kernel_name.argtypes = []
     lib.ofl_splat_tiled_pass_images.restype = ctypes.c_int64
     lib.ofl_splat_tiled_fallback_images.restype = ctypes.c_int64
+    lib.ofl_flow_corr_lookup_cells.restype = ctypes.c_int64
     _lib = lib
     return lib
 

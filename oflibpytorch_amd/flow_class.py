@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _census, _consistency, _cost_volume, _native, _photometric, _smoothness, _ssim, distributed
+from . import _census, _consistency, _corr_lookup, _cost_volume, _native, _photometric, _smoothness, _ssim, distributed
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
@@ -1711,6 +1711,80 @@ class Flow(object):
             raise TypeError(err + "Consider_mask needs to be boolean")
         feats = [(ft if ft.device == self._device else ft.to(self._device)).contiguous() for ft in feats]      # (they keep their grad_fn)
         return _cost_volume.cost_volume(self._fv, (self._mask if consider_mask else None), feats[0], feats[1],
+                                        -1.0 if self._ref == 's' else 1.0, radius).to(self._device)
+
+    def corr_lookup(self, feat, other, radius: int = None, levels: int = None, consider_mask: bool = None) -> torch.Tensor:
+        """The correlation lookup of RAFT-style networks (RAFT, GMA, SEA-RAFT, CRAFT), computed on the fly at the looked-up positions:
+        the all-pairs volume is never formed.  `feat` holds the features on this flow's own grid, float32 C-H-W (one image for the
+        whole batch) or N-C-H-W.  `other` holds the features of the frame the flow points into: either one tensor like `feat`, with the
+        same C and H-W, from which `levels` levels (1 to 6, default 4) are made by `corr_pyramid` (avg_pool2d(2, 2), in torch, so that
+        the gradient flows back through the pooling), or a sequence of level tensors N-C-H_l-W_l / C-H_l-W_l of any sizes of at least
+        1 x 1 with the same C (`levels` is then ignored).  `radius` r is 1, 2, 3 or 4 (default 4).  Returns float32 N-(L D)-H-W on the
+        flow's device, D = (2 r + 1)^2: entry l D + (dx + r) (2 r + 1) + dy + r at pixel p is the bilinear sample (zeros outside the
+        level) of the correlation feat(p) . other_l / sqrt(C) at (p + flow(p)) / 2^l + (dx, dy) for an 's' flow, p - flow(p) for a 't'
+        flow -- the x offset is the outer index, RAFT's channel order.  All entries of a pixel are 0 where it is not valid in this
+        flow's mask (with `consider_mask` False: the mask is ignored) or a vector component is not finite.  One launch of
+        ofl_corr_lookup.hip per level, every sum in a fixed float32 order (bitwise reproducible, independent of the batch; DESIGN.md
+        3.25), nothing is read back to the host.  Differentiable with respect to `feat` and `other` (or each level tensor), by gathers
+        without atomics; NOT differentiable with respect to the flow vectors or the mask: RAFT detaches the coordinates before every
+        lookup.  16-bit and channels_last features are not supported."""
+        err = "Error computing correlation lookup: "
+
+        def as_tensor(name, ft):
+            if isinstance(ft, np.ndarray):
+                if ft.dtype != np.float32:
+                    raise TypeError(err + name + " needs to be of dtype float32")
+                ft = torch.from_numpy(ft)
+            if not isinstance(ft, torch.Tensor):
+                raise TypeError(err + name + " needs to be a torch tensor or a numpy array")
+            if ft.dtype != torch.float32:
+                raise TypeError(err + name + " needs to be of dtype float32")
+            if ft.dim() not in (3, 4):
+                raise ValueError(err + name + " needs to have 3 or 4 dimensions, C-H-W or N-C-H-W")
+            if ft.shape[-3] < 1:
+                raise ValueError(err + name + " needs to have at least 1 channel")
+            if ft.dim() == 4 and ft.shape[0] != self.shape[0]:
+                raise ValueError(err + name + " needs to have the batch size of the flow")
+            return ft
+        feat = as_tensor("Feat", feat)
+        if tuple(feat.shape[-2:]) != tuple(self.shape[1:]):
+            raise ValueError(err + "Feat needs to have the H-W shape of the flow")
+        pyramid = isinstance(other, (list, tuple))
+        if pyramid:
+            if not 1 <= len(other) <= _corr_lookup.MAX_LEVELS:
+                raise ValueError(err + "Other needs to hold 1 to 6 levels")
+            level_list = [as_tensor("Other level %d" % l, lv) for l, lv in enumerate(other)]
+            for l, lv in enumerate(level_list):
+                if lv.shape[-2] < 1 or lv.shape[-1] < 1:
+                    raise ValueError(err + "Other level %d is empty" % l)
+        else:
+            other = as_tensor("Other", other)
+            if tuple(other.shape[-2:]) != tuple(self.shape[1:]):
+                raise ValueError(err + "Other needs to have the H-W shape of the flow")
+            level_list = [other]
+        for lv in level_list:
+            if lv.shape[-3] != feat.shape[-3]:
+                raise ValueError(err + "Feat and other need to have the same number of channels")
+        radius = _corr_lookup.RADIUS if radius is None else radius
+        if not isinstance(radius, int) or isinstance(radius, bool):
+            raise TypeError(err + "Radius needs to be an integer")
+        if not 1 <= radius <= _corr_lookup.MAX_RADIUS:
+            raise ValueError(err + "Radius needs to be 1, 2, 3 or 4")
+        if not pyramid:
+            levels = _corr_lookup.LEVELS if levels is None else levels
+            if not isinstance(levels, int) or isinstance(levels, bool):
+                raise TypeError(err + "Levels needs to be an integer")
+            if not 1 <= levels <= _corr_lookup.MAX_LEVELS:
+                raise ValueError(err + "Levels needs to be 1 to 6")
+            if min(other.shape[-2:]) >> (levels - 1) < 1:
+                raise ValueError(err + "Other level %d is empty" % (levels - 1))
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError(err + "Consider_mask needs to be boolean")
+        to_dev = lambda ft: (ft if ft.device == self._device else ft.to(self._device)).contiguous()      # (they keep their grad_fn)
+        feat = to_dev(feat)
+        level_list = [to_dev(lv) for lv in level_list] if pyramid else _corr_lookup.corr_pyramid(to_dev(other), levels)
+        return _corr_lookup.corr_lookup(self._fv, (self._mask if consider_mask else None), feat, level_list,
                                         -1.0 if self._ref == 's' else 1.0, radius).to(self._device)
 
     # ------------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@ from typing import Union
 import numpy as np
 import torch
 
+from ._corr_lookup import corr_pyramid  # noqa: F401  (exported by the package)
 from .flow_class import Flow
 from .utils import get_valid_ref
 
@@ -169,6 +170,16 @@ def flow_cost_volume(flow, feat, other, ref: str, mask=None, radius: int = None)
     the features `other` of the frame it points into, float32 N-D-H-W with D = (2 radius + 1)^2 (D-H-W for 3-D input), differentiable
     with respect to tensor `flow`, `feat` and `other`.  An extension: the reference has no such function."""
     v = Flow(flow, ref, mask).cost_volume(feat, other, radius=radius)
+    return v if len(flow.shape) > 3 else v.squeeze(0)
+
+
+def flow_corr_lookup(flow, feat, other, ref: str, mask=None, radius: int = None, levels: int = None) -> torch.Tensor:
+    """Flow(flow, ref, mask).corr_lookup(feat, other, radius, levels): RAFT's correlation lookup between the features `feat` on the
+    flow's grid and the features `other` (one tensor, pooled into `levels` levels, or a sequence of level tensors, e.g. from
+    `corr_pyramid`) of the frame it points into, float32 N-(L D)-H-W with D = (2 radius + 1)^2 ((L D)-H-W for 3-D input),
+    differentiable with respect to tensor `feat` and `other`, not `flow`.  An extension: the reference has no such
+    function."""
+    v = Flow(flow, ref, mask).corr_lookup(feat, other, radius=radius, levels=levels)
     return v if len(flow.shape) > 3 else v.squeeze(0)
 
 
