@@ -1209,6 +1209,41 @@ int ofl_flow_corr_lookup_grad_other_f32(const float* feat, int64_t feat_bs, int3
                                         int32_t level_w, const float* nodes, const int64_t* order, const int64_t* starts,
                                         float* grad_other, int32_t n, int32_t h, int32_t w, void* stream);
 
+/*
+ * The convex upsampling of RAFT-style networks (RAFT, GMA, CRAFT, SEA-RAFT, FlowFormer, RAFT-Stereo), one streaming pass (DESIGN.md 3.26,
+ * which defines the numbers; ofl_upsample.hip): Flow.upsample_convex.  An extension: the reference has no such function.  flow, flow_bs
+ * and flow_half as for ofl_flow_photometric_f64, but h and w may be 1; `logits` fp32 [n][9 K^2][h w], contiguous, K = `factor`, 2, 4 or 8:
+ * channel t K^2 + i K + j belongs to tap t = 3 (dy + 1) + (dx + 1), dy, dx = -1 .. 1, sub-row i and sub-column j (RAFT's order).  For the
+ * fine pixel (K y + i, K x + j), every step float64 with one rounding per operation unless said otherwise:
+ *   m        the maximum of the nine logits by a running float32 compare: m = l_0; m = (l_t > m) ? l_t : m
+ *   e_t      = exp((double)l_t - (double)m);  s = (((e_0 + e_1) + ...) + e_8);  w_t = e_t / s
+ *   F_{c,t}  = K * (double)f_c(y + dy, x + dx), exact; +0, selected and not loaded, where the neighbour lies outside the coarse frame
+ *   o_c      = sum over t ascending, from +0, of w_t * F_{c,t}: each product rounded, then the sum (no fused multiply-add)
+ * The mask does not enter the arithmetic.  Inputs are never written.
+ *
+ * ofl_flow_upsample_convex_f32: out fp32 [n][2][K h][K w] = (float)o_c, every element WRITTEN; with a mask ([*,h,w] bytes, stride mask_bs)
+ *   out_mask bytes [n][K h][K w], every element WRITTEN: (mask(y, x) != 0) over the K x K block of the coarse pixel.  mask and out_mask
+ *   are both given or both NULL.  One launch.
+ * ofl_flow_upsample_convex_grad_f32: with the upstream gradient grad_out fp32 [n][2][K h][K w] and G_c = (double)grad_out_c:
+ *   grad_logits (NULL: not made) fp32 [n][9 K^2][h w], every element WRITTEN:
+ *     (float)( w_t * ((G_0 * F_{0,t} + G_1 * F_{1,t}) - (G_0 * o_0 + G_1 * o_1)) ), w and o as in the forward
+ *   grad_flow (NULL: not made) fp32 [n][2][h w], every element WRITTEN, a gather without atomics:
+ *     grad_flow_c(q) = (float)( K * sum over t, then i, then j ascending, from +0, of w_t(i, j; q - delta_t) * G_c(q - delta_t; i, j) ),
+ *     over the taps whose coarse pixel q - delta_t lies in the frame, delta_t = (dy, dx) of tap t
+ *   workspace: float64 [n][2][K h][K w], required exactly when grad_flow is given; the first launch WRITES m and s of every fine pixel
+ *   to it and the second reads them (w_t = exp((double)l_t - m) / s).  Two launches, or one without grad_flow.
+ *
+ * OFL_E_ARG, before any launch, for: a factor other than 2, 4, 8, n outside 1 .. 65535, h or w < 1, (K h) * (K w) >= 2^31, a NULL
+ * required pointer, mask without out_mask or the reverse, grad_flow without workspace or the reverse, neither gradient, a negative
+ * stride, a flow_half that is neither 0 nor 1, a pointer not aligned to its element (out and grad_out: to 16 bytes, out_mask: to 8).
+ */
+int ofl_flow_upsample_convex_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
+                                 const float* logits, int32_t factor, float* out, uint8_t* out_mask, int32_t n, int32_t h, int32_t w,
+                                 void* stream);
+int ofl_flow_upsample_convex_grad_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const float* logits, int32_t factor,
+                                      const float* grad_out, float* grad_logits, float* grad_flow, double* workspace, int32_t n, int32_t h,
+                                      int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,14 +25,18 @@ other over a window of radius 1 to 4, warp and correlation from LDS tiles in one
 tensors and the vectors (not in the reference).  `Flow.corr_lookup`, `flow_corr_lookup` and
 `corr_pyramid` give the correlation lookup of RAFT-style networks -- feat(p) . other_l / sqrt(C) sampled bilinearly around
 (p + flow(p)) / 2^l on every pyramid level, computed on the fly without the all-pairs volume -- differentiable with respect to both
-feature tensors, not the vectors (not in the reference).  No CPU fallback: see `_native.NativeUnavailable`.
+feature tensors, not the vectors (not in the reference).  `Flow.upsample_convex` and `upsample_flow_convex` give the
+learned convex upsampling that ends every refinement iteration of such a network -- each of the k x k fine pixels of a coarse pixel mixes
+the 3 x 3 neighbourhood of k flow under the softmax of its nine predicted logits, k = 2, 4 or 8, in one streaming pass --
+differentiable with respect to the logits and the vectors (not in the reference).  No CPU fallback: see
+`_native.NativeUnavailable`.
 """
 from .flow_class import Flow, set_revalidate_every_call, get_revalidate_every_call
 from .flow_operations import (combine_flows, switch_flow_ref, invert_flow, valid_target, valid_source, batch_flows,
                               get_flow_padding, visualise_flow, visualise_flow_arrows, get_flow_matrix,
                               flow_error_stats, flow_epe, flow_consistency, flow_smoothness, flow_smoothness_stats,
                               flow_photometric, flow_photometric_stats, flow_census, flow_census_stats,
-                              flow_ssim, flow_ssim_stats, flow_cost_volume, flow_corr_lookup, corr_pyramid)
+                              flow_ssim, flow_ssim_stats, flow_cost_volume, flow_corr_lookup, corr_pyramid, upsample_flow_convex)
 from .utils import (from_matrix, from_transforms, load_kitti, load_sintel, load_sintel_mask, resize_flow, apply_flow, is_zero_flow, get_pure_pytorch,
                     set_pure_pytorch, unset_pure_pytorch, to_numpy, to_tensor, move_axis, apply_s_flow,
                     grid_from_unstructured_data, get_flow_endpoints, threshold_vectors, normalise_coords, track_pts,

@@ -12,7 +12,7 @@ implemented (`once_differentiable` raises).
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _census, _corr_lookup, _cost_volume, _native, _photometric, _smoothness, _ssim
+from . import _census, _corr_lookup, _cost_volume, _native, _photometric, _smoothness, _ssim, _upsample
 
 
 def _reduce_to(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
@@ -365,3 +365,29 @@ class CorrLookupFn(torch.autograd.Function):
         like = lambda grad, t: _reduce_to(grad, t[None])[0] if t.dim() == 3 else _reduce_to(grad, t)      # C-H-W: summed over the batch
         return (None, None, like(g_feat, feat) if need_feat else None, None, None) + tuple(
             like(gl, lv) if need else None for gl, lv, need in zip(g_levels, levels, need_levels))
+
+
+class UpsampleConvexFn(torch.autograd.Function):
+    """out[n, c, k y + i, k x + j] = sum_t softmax_t(logits[n, t k^2 + i k + j, y, x]) * k * vecs_c(y + dy, x + dx), RAFT's convex
+    upsampling (Flow.upsample_convex), and the mask of the coarse pixel over its k x k block (or None).  Differentiable
+    with respect to the logits and the vectors, not the mask: d logits is local to the fine pixel, d vecs a gather in a fixed order, both
+    bitwise reproducible.  The binding is looked up by name at every call: the host tests replace `_upsample.flow_*` with fakes after
+    this class exists."""
+
+    @staticmethod
+    def forward(ctx, vecs, mask, logits, factor):
+        out, out_mask = _upsample.flow_upsample_convex(vecs.detach(), mask, logits.detach(), factor)
+        ctx.save_for_backward(vecs, logits)
+        ctx.factor = factor
+        if out_mask is not None:
+            ctx.mark_non_differentiable(out_mask)
+        return out, out_mask
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_mask=None):
+        vecs, logits = ctx.saved_tensors
+        need_vecs, need_logits = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        d_logits, d_vecs = _upsample.flow_upsample_convex_grad(vecs.detach(), logits.detach(), ctx.factor, g, want_logits=bool(need_logits),
+                                                               want_vecs=bool(need_vecs))
+        return (_reduce_to(d_vecs, vecs) if need_vecs else None, None, _reduce_to(d_logits, logits) if need_logits else None, None)

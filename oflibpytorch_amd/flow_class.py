@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _census, _consistency, _corr_lookup, _cost_volume, _native, _photometric, _smoothness, _ssim, distributed
+from . import _census, _consistency, _corr_lookup, _cost_volume, _native, _photometric, _smoothness, _ssim, _upsample, distributed
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
@@ -1786,6 +1786,54 @@ class Flow(object):
         level_list = [to_dev(lv) for lv in level_list] if pyramid else _corr_lookup.corr_pyramid(to_dev(other), levels)
         return _corr_lookup.corr_lookup(self._fv, (self._mask if consider_mask else None), feat, level_list,
                                         -1.0 if self._ref == 's' else 1.0, radius).to(self._device)
+
+    def upsample_convex(self, weights, factor: int = None, consider_mask: bool = None) -> FlowAlias:
+        """The learned convex upsampling that ends every refinement iteration of RAFT-style networks (RAFT, GMA, CRAFT, SEA-RAFT,
+        FlowFormer, RAFT-Stereo): `weights` holds the 9 k^2 logits the network predicts per pixel of this (coarse) flow, float32
+        N-(9 k^2)-H-W, or (9 k^2)-H-W for a batch of 1, in RAFT's channel order -- channel t k^2 + i k + j belongs to tap
+        t = 3 (dy + 1) + (dx + 1), sub-row i and sub-column j.  `factor` k is 2, 4 or 8 and is inferred from the channel count when None.
+        Returns a flow of shape N-(k H)-(k W) with the same reference and device: fine pixel (k y + i, k x + j) is the mix of the 3 x 3
+        neighbourhood of k flow(y, x), zeros outside the frame, under the softmax of its nine logits.  Its mask is this flow's, every bit
+        replicated over its k x k block (with `consider_mask` False: no mask, i.e. all True); masked pixels still lend their vectors to
+        their neighbours.  One launch of ofl_upsample.hip, float64 arithmetic in a fixed order rounded once, bitwise
+        reproducible and independent of the batch.  Differentiable with respect to the logits and the flow vectors, without atomics;
+        not with respect to the mask.  16-bit and channels_last logits, other factors and other neighbourhoods are not supported: under
+        autocast the caller casts the logits, as RAFT's own `.float()` does."""
+        err = "Error upsampling flow: "
+        if isinstance(weights, np.ndarray):
+            if weights.dtype != np.float32:
+                raise TypeError(err + "Weights need to be of dtype float32")
+            weights = torch.from_numpy(weights)
+        if not isinstance(weights, torch.Tensor):
+            raise TypeError(err + "Weights need to be a torch tensor or a numpy array")
+        if weights.dtype != torch.float32:
+            raise TypeError(err + "Weights need to be of dtype float32")
+        if weights.dim() not in (3, 4):
+            raise ValueError(err + "Weights need to have 3 or 4 dimensions, (9 k^2)-H-W or N-(9 k^2)-H-W")
+        if weights.dim() == 3:
+            weights = weights.unsqueeze(0)
+        channels = int(weights.shape[1])
+        if channels not in [9 * k * k for k in _upsample.FACTORS]:
+            raise ValueError(err + "Weights need to have 9 k^2 channels with k 2, 4 or 8, but got {}".format(channels))
+        if factor is not None:
+            if isinstance(factor, bool) or not isinstance(factor, int):
+                raise TypeError(err + "Factor needs to be an integer")
+            if factor not in _upsample.FACTORS:
+                raise ValueError(err + "Factor needs to be 2, 4 or 8")
+            if 9 * factor * factor != channels:
+                raise ValueError(err + "Factor {} contradicts the {} channels of the weights".format(factor, channels))
+        factor = _upsample.factor_of(channels)
+        if weights.shape[0] != self.shape[0]:
+            raise ValueError(err + "Weights need to have the batch size of the flow")
+        if tuple(weights.shape[-2:]) != tuple(self.shape[1:]):
+            raise ValueError(err + "Weights need to have the H-W shape of the flow")
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError(err + "Consider_mask needs to be boolean")
+        if weights.device != self._device:
+            weights = weights.to(self._device)              # (keeps its grad_fn)
+        out, out_mask = _upsample.upsample_convex(self._fv, (self._mask if consider_mask else None), weights, factor)
+        return Flow(out, self._ref, out_mask, device=self._device)
 
     # ------------------------------------------------------------------------------------------
     # composition (flow_class.py:1648-1810)

@@ -183,6 +183,15 @@ def flow_corr_lookup(flow, feat, other, ref: str, mask=None, radius: int = None,
     return v if len(flow.shape) > 3 else v.squeeze(0)
 
 
+def upsample_flow_convex(flow, weights, factor: int = None) -> torch.Tensor:
+    """Flow(flow).upsample_convex(weights, factor).vecs: RAFT's learned convex upsampling of the vectors `flow` (2-H-W or N-2-H-W,
+    tensor or array) under the 9 k^2 logits `weights` per pixel, float32 N-2-(k H)-(k W) (2-(k H)-(k W) for 3-D input), differentiable
+    with respect to tensor `flow` and `weights`.  The arithmetic does not depend on the flow's reference.  An extension (DESIGN.md
+    3.26): the reference has no such function."""
+    v = Flow(flow).upsample_convex(weights, factor=factor, consider_mask=False).vecs
+    return v if len(flow.shape) > 3 else v.squeeze(0)
+
+
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
     """Concatenate flow objects of equal H, W, ref and device along the batch axis (flow_operations.py:458-483)"""
     if not isinstance(flows, (list, tuple)):
