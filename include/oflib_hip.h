@@ -1244,6 +1244,40 @@ int ofl_flow_upsample_convex_grad_f32(const void* flow, int64_t flow_bs, int32_t
                                       const float* grad_out, float* grad_logits, float* grad_flow, double* workspace, int32_t n, int32_t h,
                                       int32_t w, void* stream);
 
+/*
+ * The global matching of GMFlow-style networks (GMFlow, UniMatch, matching heads of tracking and stereo networks), streamed without the
+ * (h w)^2 volume (which defines the numbers; ofl_matching.hip): Flow.from_matching.  An extension: the reference has no
+ * such function.  `feat` and `other` fp32 [*,C,h,w], planes contiguous, feat_bs / other_bs elements between images (0: one image for the
+ * whole batch), C = `channels` >= 1, h, w >= 1; flow_sign -1 for an 's' flow, +1 for a 't' flow.  For pixel p = (y, x) and every position
+ * q = (qy, qx) of `other` in ascending raster order:
+ *   s_q      = (sum over c ascending, from +0, of feat_c(p) * other_c(q)) / sqrtf((float)C): float32, each product rounded, then the sum
+ *   chain    m float32; S, X, Y float64, one rounding per operation.  At q = 0: m = s_0, S = X = Y = +0.  For every q: if s_q > m then
+ *            r = exp((double)m - (double)s_q), S = S r, X = X r, Y = Y r, m = s_q; then e = exp((double)s_q - (double)m), S = S + e,
+ *            X = X + e (double)qx, Y = Y + e (double)qy
+ *   result   ox = X / S, oy = Y / S; u = (float)((ox - (double)x) * -flow_sign), v = (float)((oy - (double)y) * -flow_sign);
+ *            prob = (float)(1.0 / S)
+ * Inputs are never written.
+ *
+ * ofl_flow_global_match_f32: out fp32 [n][2][h w] = (u, v), every element WRITTEN; prob (NULL: not made) fp32 [n][h w], every element
+ *   WRITTEN; workspace (NULL: no backward will follow) 28 n h w bytes, 8-byte aligned, every byte WRITTEN: float64 [3][n][h w] = S, ox, oy,
+ *   then float32 [n][h w] = m.  One launch.
+ * ofl_flow_global_match_grad_f32: with the workspace of the forward of the same operands, the upstream gradient grad_out fp32 [n][2][h w]
+ *   and G = -flow_sign * (double)grad_out of p, per pair:  w = exp((double)s_q - (double)m) / S,
+ *   ds = (float)(w * ((G_x * ((double)qx - ox)) + (G_y * ((double)qy - oy)))),  dss = ds / sqrtf((float)C), and
+ *     grad_feat  (NULL: not made) fp32 [n][C][h w], every element WRITTEN: sum over q ascending, from +0, of dss(p, q) * other_c(q)
+ *     grad_other (NULL: not made) fp32 [n][C][h w], every element WRITTEN: sum over p ascending, from +0, of dss(p, q) * feat_c(p)
+ *   float32 products and one float32 sum per element, no atomics.  One launch per gradient; any C (a launch walks the frame once per 128
+ *   channels).
+ *
+ * OFL_E_ARG, before any launch, for: n outside 1 .. 65535, h or w outside 1 .. 2^24, h * w >= 2^31, C < 1, a flow_sign other than +-1, a
+ * NULL required pointer, neither gradient, a negative stride, a pointer not aligned to its element (the workspace: to 8 bytes).
+ */
+int ofl_flow_global_match_f32(const float* feat, int64_t feat_bs, const float* other, int64_t other_bs, int32_t channels, float flow_sign,
+                              float* out, float* prob, void* workspace, int32_t n, int32_t h, int32_t w, void* stream);
+int ofl_flow_global_match_grad_f32(const float* feat, int64_t feat_bs, const float* other, int64_t other_bs, int32_t channels,
+                                   float flow_sign, const void* workspace, const float* grad_out, float* grad_feat, float* grad_other,
+                                   int32_t n, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ implemented (`once_differentiable` raises).
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _census, _corr_lookup, _cost_volume, _native, _photometric, _smoothness, _ssim, _upsample
+from . import _census, _corr_lookup, _cost_volume, _matching, _native, _photometric, _smoothness, _ssim, _upsample
 
 
 def _reduce_to(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
@@ -391,3 +391,30 @@ class UpsampleConvexFn(torch.autograd.Function):
         d_logits, d_vecs = _upsample.flow_upsample_convex_grad(vecs.detach(), logits.detach(), ctx.factor, g, want_logits=bool(need_logits),
                                                                want_vecs=bool(need_vecs))
         return (_reduce_to(d_vecs, vecs) if need_vecs else None, None, _reduce_to(d_logits, logits) if need_logits else None, None)
+
+
+class GlobalMatchFn(torch.autograd.Function):
+    """flow(p) = -flow_sign * (sum_q softmax_q(feat(p) . other(q) / sqrt(C)) q - p) and the matching probability 1 / S of every pixel
+    (or None), GMFlow's global matching (Flow.from_matching).  Differentiable with respect to `feat` and `other`, not
+    through the probability: both gradients recompute the logits on the saved maximum and sum, every sum in a fixed order, bitwise
+    reproducible.  The binding is looked up by name at every call: the host tests replace `_matching.flow_*` with fakes after this
+    class exists."""
+
+    @staticmethod
+    def forward(ctx, feat, other, flow_sign, want_prob):
+        out, prob, stats = _matching.flow_global_match(feat.detach(), other.detach(), flow_sign, want_prob, True)
+        ctx.save_for_backward(feat, other, stats)
+        ctx.flow_sign = flow_sign
+        if prob is not None:
+            ctx.mark_non_differentiable(prob)
+        return out, prob
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_prob=None):
+        feat, other, stats = ctx.saved_tensors
+        need_feat, need_other = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        d_feat, d_other = _matching.flow_global_match_grad(feat.detach(), other.detach(), ctx.flow_sign, stats, g,
+                                                           want_feat=bool(need_feat), want_other=bool(need_other))
+        like = lambda grad, t: _reduce_to(grad, t[None])[0] if t.dim() == 3 else _reduce_to(grad, t)      # C-H-W: the batch of one
+        return (like(d_feat, feat) if need_feat else None, like(d_other, other) if need_other else None, None, None)

@@ -20,7 +20,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _census, _consistency, _corr_lookup, _cost_volume, _native, _photometric, _smoothness, _ssim, _upsample, distributed
+from . import (_census, _consistency, _corr_lookup, _cost_volume, _matching, _native, _photometric, _smoothness, _ssim, _upsample,
+               distributed)
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
@@ -444,6 +445,44 @@ class Flow(object):
         device = get_valid_device(device) if device is not None else None
         on = device if (device is not None and device.type == 'cuda') else None
         return cls(from_transforms(transform_list, shape, ref, padding, _device=on), ref, mask, device)
+
+    @classmethod
+    def from_matching(cls, feat, other, ref: str = None, mask=None, return_prob: bool = None):
+        """The flow between two frames by global matching of their features, as in GMFlow, UniMatch and the matching heads of tracking
+        and stereo networks: `feat` and `other` are float32 tensors of one shape, C-H-W or N-C-H-W.  For every pixel p of `feat` the
+        softmax over ALL positions q of `other` of feat(p) . other(q) / sqrt(C) gives the expected position of its match; the vector
+        of an 's' flow at p is that position minus p, the vector of a 't' flow (the default `ref`) its negation, with the meaning the
+        reference has in `Flow.corr_lookup`.  Returns a flow of shape N-H-W on the features' device with `mask` handed to the constructor
+        unchanged; with `return_prob` True a tuple of that flow and the matching probability, float32 N-H-W: the softmax weight of the
+        best match of every pixel, the value GMFlow returns as `prob`.  One launch of ofl_matching.hip that streams `other` past tiles of
+        pixels with a running maximum and three running float64 sums per pixel: the (H W)^2 volume is never formed and no logit is
+        written to memory; every sum has a fixed order, bitwise reproducible and independent of the batch.
+        Differentiable with respect to `feat` and `other`, by kernels that recompute the logits, without atomics;
+        NOT through the probability.  16-bit and channels_last features, a mask over the positions of `other`, a local window, another
+        temperature and the 1-D variant are not supported."""
+        err = "Error matching flow: "
+        for name, ft in (("Feat", feat), ("Other", other)):
+            if not isinstance(ft, torch.Tensor):
+                raise TypeError(err + name + " needs to be a torch tensor")
+            if ft.dtype != torch.float32:
+                raise TypeError(err + name + " needs to be of dtype float32")
+        return_prob = False if return_prob is None else return_prob
+        if not isinstance(return_prob, bool):
+            raise TypeError(err + "Return_prob needs to be boolean")
+        if feat.dim() not in (3, 4):
+            raise ValueError(err + "Feat needs to have 3 or 4 dimensions, C-H-W or N-C-H-W")
+        if tuple(feat.shape) != tuple(other.shape):
+            raise ValueError(err + "Feat and other need to have the same shape")
+        if min(feat.shape) < 1:
+            raise ValueError(err + "Feat and other must not be empty")
+        if ref is not None and (not isinstance(ref, str) or ref not in ('s', 't')):
+            raise ValueError(err + "Ref needs to be 's' or 't', but got {}".format(ref))
+        ref = 't' if ref is None else ref
+        if other.device != feat.device:
+            other = other.to(feat.device)                   # (keeps its grad_fn)
+        out, prob = _matching.global_match(feat, other, -1.0 if ref == 's' else 1.0, return_prob)
+        flow = cls(out, ref, mask, device=feat.device)
+        return (flow, prob.to(feat.device)) if return_prob else flow
 
     @classmethod
     def from_kitti(cls, path, load_valid: bool = None, device=None) -> FlowAlias:
