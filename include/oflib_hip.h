@@ -1278,6 +1278,58 @@ int ofl_flow_global_match_grad_f32(const float* feat, int64_t feat_bs, const flo
                                    float flow_sign, const void* workspace, const float* grad_out, float* grad_feat, float* grad_other,
                                    int32_t n, int32_t h, int32_t w, void* stream);
 
+/* ---- flow propagation by attention -----------------------------------------------------------------------------------------------
+ * flow'(p) = sum_q softmax_q(query(p) . key(q) / sqrt(C)) flow(q), GMFlow's and UniMatch's propagation of matched vectors by
+ * self-attention, over ALL positions q (global) or over the (2 radius + 1)^2 window of p with zero padding (local), without the (h w)^2
+ * volume and without an unfold (which defines the numbers; ofl_propagate.hip): Flow.propagate.  An extension: the
+ * reference has no such function.  `query` and `key` fp32 [*,C,h,w], `flow` fp32 [*,2,h,w] = (u, v), `mask` (NULL: nothing is excluded)
+ * bytes [*,h,w], planes contiguous, *_bs elements between images (0: one image for the whole batch), C = `channels` >= 1, h, w >= 1.
+ * A position q inside the frame is EXCLUDED where its mask byte is 0.
+ *   s(p, q)  = (sum over c ascending, from +0, of query_c(p) * key_c(q)) / sqrtf((float)C): float32, each product rounded, then the sum
+ *   global   the chain of ofl_flow_global_match_f32 over the positions that are not excluded, in ascending raster order: m float32; S, X,
+ *            Y float64.  The first participating position sets m = s, S = X = Y = +0; every step: if s > m then r = exp((double)m -
+ *            (double)s), S = S r, X = X r, Y = Y r, m = s; then e = exp((double)s - (double)m), S = S + e, X = X + e (double)u(q),
+ *            Y = Y + e (double)v(q).  An excluded position contributes no step
+ *   local    the offsets (dy, dx), dy outermost, both ascending from -radius.  A position outside the frame takes part with the logit +0
+ *            and the vector (0, 0), whatever the mask.  Two passes: m = the first participating logit, replaced by every later one with
+ *            s > m; then S, X, Y as above in offset order on that final m, without a rescale
+ *   result   ox = X / S, oy = Y / S; out = ((float)ox, (float)oy).  A pixel is EMPTY when no position inside the frame takes part: its
+ *            result is (+0, +0), its byte of `valid` 0 (every other pixel: 1), its statistics S = 0, m = ox = oy = +0
+ * Inputs are never written.
+ *
+ * ofl_flow_propagate_global_f32 / ofl_flow_propagate_local_f32: out fp32 [n][2][h w], every element WRITTEN; valid (NULL: not made) bytes
+ *   [n][h w], every element WRITTEN; workspace (NULL: no backward will follow) 28 n h w bytes, 8-byte aligned, every byte WRITTEN: float64
+ *   [3][n][h w] = S, ox, oy, then float32 [n][h w] = m.  One launch.
+ * ofl_flow_propagate_global_grad_f32 / ofl_flow_propagate_local_grad_f32: with the workspace of the forward of the same operands and the
+ *   upstream gradient grad_out fp32 [n][2][h w] = (g_x, g_y), per pair:  w = exp((double)s - (double)m) / S,
+ *   ds = (float)(w * (((double)g_x * ((double)u(q) - ox)) + ((double)g_y * ((double)v(q) - oy)))),  dss = ds / sqrtf((float)C),
+ *   tx = (float)(w * (double)g_x), ty = (float)(w * (double)g_y); dss, tx and ty are exactly +0 where q is excluded or p is empty, and
+ *     grad_query (NULL: not made) fp32 [n][C][h w], every element WRITTEN: sum over q in forward order, from +0, of dss(p, q) * key_c(q)
+ *     grad_key   (NULL: not made) fp32 [n][C][h w], every element WRITTEN: sum over p ascending, from +0, of dss(p, q) * query_c(p)
+ *     grad_flow  (NULL: not made) fp32 [n][2][h w], every element WRITTEN: sum over p ascending, from +0, of tx(p, q); of ty(p, q)
+ *   float32 products and one float32 sum per element, no atomics; a position outside the frame has no gradient.  Global: one launch
+ *   for grad_query and one for grad_key and grad_flow together, each recomputing the logits.  Local: `scratch` fp32 [n][k][(2 radius +
+ *   1)^2][h w], k = 3 with grad_flow and 1 without, every element WRITTEN by a first launch (dss, tx, ty per offset), from which the
+ *   gradients are gathered by one launch for grad_query and one for grad_key and grad_flow.
+ *
+ * OFL_E_ARG, before any launch, for: n outside 1 .. 65535, h or w outside 1 .. 2^24, h * w >= 2^31, C < 1, a radius outside 1 .. 4, a
+ * NULL required pointer, no gradient at all, a negative stride, a pointer not aligned to its element (the workspace: to 8 bytes).
+ */
+int ofl_flow_propagate_global_f32(const float* query, int64_t query_bs, const float* key, int64_t key_bs, int32_t channels,
+                                  const float* flow, int64_t flow_bs, const uint8_t* mask, int64_t mask_bs, float* out, uint8_t* valid,
+                                  void* workspace, int32_t n, int32_t h, int32_t w, void* stream);
+int ofl_flow_propagate_global_grad_f32(const float* query, int64_t query_bs, const float* key, int64_t key_bs, int32_t channels,
+                                       const float* flow, int64_t flow_bs, const uint8_t* mask, int64_t mask_bs, const void* workspace,
+                                       const float* grad_out, float* grad_query, float* grad_key, float* grad_flow, int32_t n, int32_t h,
+                                       int32_t w, void* stream);
+int ofl_flow_propagate_local_f32(const float* query, int64_t query_bs, const float* key, int64_t key_bs, int32_t channels,
+                                 const float* flow, int64_t flow_bs, const uint8_t* mask, int64_t mask_bs, int32_t radius, float* out,
+                                 uint8_t* valid, void* workspace, int32_t n, int32_t h, int32_t w, void* stream);
+int ofl_flow_propagate_local_grad_f32(const float* query, int64_t query_bs, const float* key, int64_t key_bs, int32_t channels,
+                                      const float* flow, int64_t flow_bs, const uint8_t* mask, int64_t mask_bs, int32_t radius,
+                                      const void* workspace, const float* grad_out, float* scratch, float* grad_query, float* grad_key,
+                                      float* grad_flow, int32_t n, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

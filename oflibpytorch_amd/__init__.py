@@ -31,7 +31,11 @@ the 3 x 3 neighbourhood of k flow under the softmax of its nine predicted logits
 differentiable with respect to the logits and the vectors (not in the reference).  `Flow.from_matching` and
 `global_matching_flow` give the first flow of a matching-style network (GMFlow, UniMatch) -- for every pixel the softmax over ALL
 positions of the other frame of feat(p) . other(q) / sqrt(C), the expected position minus p, and the matching probability, streamed
-without the (H W)^2 volume -- differentiable with respect to both feature tensors (not in the reference).  No CPU fallback: see
+without the (H W)^2 volume -- differentiable with respect to both feature tensors (not in the reference).
+`Flow.propagate` and `propagate_flow` give the flow propagation by attention that follows it -- the vector at p becomes the softmax over
+all positions q, or over a zero-padded window of radius 1 to 4, of query(p) . key(q) / sqrt(C), times flow(q), with the positions the
+flow's mask excludes left out, so that matched vectors fill occluded regions -- differentiable with respect to both feature tensors and
+the vectors (not in the reference).  No CPU fallback: see
 `_native.NativeUnavailable`.
 """
 from .flow_class import Flow, set_revalidate_every_call, get_revalidate_every_call
@@ -40,7 +44,7 @@ from .flow_operations import (combine_flows, switch_flow_ref, invert_flow, valid
                               flow_error_stats, flow_epe, flow_consistency, flow_smoothness, flow_smoothness_stats,
                               flow_photometric, flow_photometric_stats, flow_census, flow_census_stats,
                               flow_ssim, flow_ssim_stats, flow_cost_volume, flow_corr_lookup, corr_pyramid, upsample_flow_convex,
-                              global_matching_flow)
+                              global_matching_flow, propagate_flow)
 from .utils import (from_matrix, from_transforms, load_kitti, load_sintel, load_sintel_mask, resize_flow, apply_flow, is_zero_flow, get_pure_pytorch,
                     set_pure_pytorch, unset_pure_pytorch, to_numpy, to_tensor, move_axis, apply_s_flow,
                     grid_from_unstructured_data, get_flow_endpoints, threshold_vectors, normalise_coords, track_pts,

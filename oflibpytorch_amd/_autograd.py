@@ -12,7 +12,7 @@ implemented (`once_differentiable` raises).
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _census, _corr_lookup, _cost_volume, _matching, _native, _photometric, _smoothness, _ssim, _upsample
+from . import _census, _corr_lookup, _cost_volume, _matching, _native, _photometric, _propagate, _smoothness, _ssim, _upsample
 
 
 def _reduce_to(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
@@ -418,3 +418,32 @@ class GlobalMatchFn(torch.autograd.Function):
                                                            want_feat=bool(need_feat), want_other=bool(need_other))
         like = lambda grad, t: _reduce_to(grad, t[None])[0] if t.dim() == 3 else _reduce_to(grad, t)      # C-H-W: the batch of one
         return (like(d_feat, feat) if need_feat else None, like(d_other, other) if need_other else None, None, None)
+
+
+class PropagateFn(torch.autograd.Function):
+    """flow'(p) = sum_q softmax_q(query(p) . key(q) / sqrt(C)) flow(q) over the positions the mask does not exclude -- all of them
+    (radius None) or the zero-padded (2 radius + 1)^2 window of p -- and the result mask (or None), GMFlow's flow propagation by
+    attention (Flow.propagate).  Differentiable with respect to the vectors, `query` and `key`, not the mask: every
+    gradient is a sum in a fixed order with one owner, bitwise reproducible.  The binding is looked up by name at every call: the host
+    tests replace `_propagate.flow_*` with fakes after this class exists."""
+
+    @staticmethod
+    def forward(ctx, vecs, mask, query, key, radius):
+        out, valid, stats = _propagate.flow_propagate(vecs.detach(), mask, query.detach(), key.detach(), radius, True)
+        ctx.save_for_backward(vecs, mask, query, key, stats)
+        ctx.radius = radius
+        if valid is not None:
+            ctx.mark_non_differentiable(valid)
+        return out, valid
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_valid=None):
+        vecs, mask, query, key, stats = ctx.saved_tensors
+        need_vecs, _, need_query, need_key = ctx.needs_input_grad[:4]
+        d_query, d_key, d_vecs = _propagate.flow_propagate_grad(vecs.detach(), mask, query.detach(), key.detach(), ctx.radius, stats, g,
+                                                                want_query=bool(need_query), want_key=bool(need_key),
+                                                                want_flow=bool(need_vecs))
+        like = lambda grad, t: _reduce_to(grad, t[None])[0] if t.dim() == 3 else _reduce_to(grad, t)      # C-H-W: summed over the batch
+        return (_reduce_to(d_vecs, vecs) if need_vecs else None, None, like(d_query, query) if need_query else None,
+                like(d_key, key) if need_key else None, None)

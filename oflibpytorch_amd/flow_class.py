@@ -20,8 +20,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import (_census, _consistency, _corr_lookup, _cost_volume, _matching, _native, _photometric, _smoothness, _ssim, _upsample,
-               distributed)
+from . import (_census, _consistency, _corr_lookup, _cost_volume, _matching, _native, _photometric, _propagate, _smoothness, _ssim,
+               _upsample, distributed)
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
@@ -1872,6 +1872,59 @@ class Flow(object):
         if weights.device != self._device:
             weights = weights.to(self._device)              # (keeps its grad_fn)
         out, out_mask = _upsample.upsample_convex(self._fv, (self._mask if consider_mask else None), weights, factor)
+        return Flow(out, self._ref, out_mask, device=self._device)
+
+    def propagate(self, query, key=None, radius: int = None, consider_mask: bool = None) -> FlowAlias:
+        """The flow propagation by self-attention of GMFlow, UniMatch and their stereo and depth siblings, which carries matched vectors
+        into occluded and out-of-frame regions: the vector at p becomes sum_q softmax_q(query(p) . key(q) / sqrt(C)) flow(q).  `query`
+        and `key` are float32 tensors, C-H-W (one image for the whole batch) or N-C-H-W, with this flow's H-W and the same C >= 1;
+        `key` None means `key` = `query` (the projections of the network are the caller's layers).  `radius` None is the global form,
+        over ALL positions q, as at 1/8 scale; `radius` 1, 2, 3 or 4 is the local form over the (2 `radius` + 1)^2 window of p, as at
+        1/4 scale, in which a position outside the frame takes part with the logit 0 and the vector (0, 0): the zero padding of
+        `unfold`, which the trained networks expect.  A position that is not valid in this flow's mask is EXCLUDED from the softmax
+        (with `consider_mask` False: none is), so the flow's invalid pixels are filled from its valid ones by feature similarity.
+        Returns a flow of the same shape, reference and device; its mask is True everywhere but at the EMPTY pixels, for which no
+        position inside the frame takes part (the whole image masked; locally, the whole window masked) and whose vector is (0, 0).
+        One launch of ofl_propagate.hip: the global form streams the key past tiles of pixels with a running maximum and three running
+        float64 sums per pixel, so that the (H W)^2 volume is never formed; the local form computes the window's logits from LDS tiles
+        without an unfold; every sum has a fixed order, bitwise reproducible and independent of the batch.
+        Differentiable with respect to `query`, `key` and the flow vectors, without atomics; not with respect to the mask.  16-bit and
+        channels_last features, another temperature, another border rule and a double backward are not supported."""
+        err = "Error propagating flow: "
+        key = query if key is None else key
+        feats = []
+        for name, ft in (("Query", query), ("Key", key)):
+            if isinstance(ft, np.ndarray):
+                if ft.dtype != np.float32:
+                    raise TypeError(err + name + " needs to be of dtype float32")
+                ft = torch.from_numpy(ft)
+            if not isinstance(ft, torch.Tensor):
+                raise TypeError(err + name + " needs to be a torch tensor or a numpy array")
+            if ft.dtype != torch.float32:
+                raise TypeError(err + name + " needs to be of dtype float32")
+            feats.append(ft)
+        for name, ft in zip(("Query", "Key"), feats):
+            if ft.dim() not in (3, 4):
+                raise ValueError(err + name + " needs to have 3 or 4 dimensions, C-H-W or N-C-H-W")
+            if ft.shape[-3] < 1:
+                raise ValueError(err + name + " needs to have at least 1 channel")
+        if feats[0].shape[-3] != feats[1].shape[-3]:
+            raise ValueError(err + "Query and key need to have the same number of channels")
+        for name, ft in zip(("Query", "Key"), feats):
+            if tuple(ft.shape[-2:]) != tuple(self.shape[1:]):
+                raise ValueError(err + name + " needs to have the H-W shape of the flow")
+            if ft.dim() == 4 and ft.shape[0] != self.shape[0]:
+                raise ValueError(err + name + " needs to have the batch size of the flow")
+        if radius is not None:
+            if not isinstance(radius, int) or isinstance(radius, bool):
+                raise TypeError(err + "Radius needs to be an integer or None")
+            if not 1 <= radius <= _propagate.MAX_RADIUS:
+                raise ValueError(err + "Radius needs to be None, 1, 2, 3 or 4")
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError(err + "Consider_mask needs to be boolean")
+        feats = [(ft if ft.device == self._device else ft.to(self._device)).contiguous() for ft in feats]      # (they keep their grad_fn)
+        out, out_mask = _propagate.propagate(self._fv, (self._mask if consider_mask else None), feats[0], feats[1], radius)
         return Flow(out, self._ref, out_mask, device=self._device)
 
     # ------------------------------------------------------------------------------------------

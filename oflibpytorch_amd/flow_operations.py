@@ -205,6 +205,20 @@ def global_matching_flow(feat, other, ref: str, return_prob: bool = None):
     return v, (prob if feat.dim() > 3 else prob.squeeze(0))
 
 
+def propagate_flow(flow, query, key=None, radius: int = None, mask=None):
+    """Flow(flow, mask=mask).propagate(query, key, radius).vecs: the vectors `flow` (2-H-W or N-2-H-W, tensor or array) propagated by
+    attention between the float32 features `query` and `key` (None: `query`), GMFlow's softmax over all positions (`radius` None) or
+    over the zero-padded (2 radius + 1)^2 window, float32 N-2-H-W (2-H-W for 3-D input), differentiable with respect to tensor `flow`,
+    `query` and `key`.  With `mask` (N-)H-W the positions where it is False are excluded from the softmax, and the result is a tuple of
+    the vectors and the result mask, bool N-H-W (H-W for 3-D input), False where nothing was left to take part.  The arithmetic does
+    not depend on the flow's reference.  An extension: the reference has no such function."""
+    res = Flow(flow, mask=mask).propagate(query, key, radius=radius, consider_mask=mask is not None)
+    v = res.vecs if len(flow.shape) > 3 else res.vecs.squeeze(0)
+    if mask is None:
+        return v
+    return v, (res.mask if len(flow.shape) > 3 else res.mask.squeeze(0))
+
+
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
     """Concatenate flow objects of equal H, W, ref and device along the batch axis (flow_operations.py:458-483)"""
     if not isinstance(flows, (list, tuple)):
