@@ -1330,6 +1330,48 @@ int ofl_flow_propagate_local_grad_f32(const float* query, int64_t query_bs, cons
                                       const void* workspace, const float* grad_out, float* scratch, float* grad_query, float* grad_key,
                                       float* grad_flow, int32_t n, int32_t h, int32_t w, void* stream);
 
+/* ---- local matching ----------------------------------------------------------------------------------------------------------------
+ * flow'(p) = flow(p) - flow_sign * E[o], E the expectation of the offsets o of the (2 radius + 1)^2 window of p under
+ * softmax_o(feat(p) . W'(p + o) / sqrt(C)), W' being `other` sampled where the flow points: the local matching of GMFlow's and UniMatch's
+ * refinement stage, without the warped tensor, the volume or the unfold (which defines the numbers;
+ * ofl_local_match.hip): Flow.match_local.  An extension: the reference has no such function.  Operands as for ofl_flow_cost_volume_f32:
+ * `flow` fp32 or fp16 [*,2,h,w], `mask` (NULL: all True) bytes [*,h,w], `feat` and `other` fp32 [*,C,h,w], *_bs elements between images
+ * (0: one image for the whole batch), flow_sign -1 ('s') or +1 ('t'), h, w >= 2.  W'_c(q) and usable(q) are those of the cost volume, bit
+ * for bit: the sample where the mask is True and the weight sum of the taps inside the frame exceeds 0.99999, +0 elsewhere (selected).
+ *   offsets  o = (dy, dx), dy outermost, both ascending from -radius.  A position p + o OUTSIDE the frame takes NO part: no step, no
+ *            gradient.  A position inside always takes part, usable or not (through W' = +0).  The centre is inside: no pixel is empty
+ *   s(p, o)  = (sum over c ascending, from +0, of feat_c(p) * W'_c(p + o)) / sqrtf((float)C): float32, each product rounded, then the sum
+ *   softmax  two passes: m = the first participating logit, replaced by every later one with s > m; then in offset order on that final m
+ *            e = exp((double)s - (double)m), S = S + e, X = X + e (double)dx, Y = Y + e (double)dy, float64 from +0
+ *   result   ox = X / S, oy = Y / S; u' = (float)((double)u + (-flow_sign) ox), v' = (float)((double)v + (-flow_sign) oy), one
+ *            rounding each; prob = (float)(1.0 / S)
+ * Inputs are never written.
+ *
+ * ofl_flow_local_match_f32: out fp32 [n][2][h w], every element WRITTEN; prob (NULL: not made) fp32 [n][h w], every element WRITTEN;
+ *   workspace (NULL: no backward will follow) 28 n h w bytes, 8-byte aligned, every byte WRITTEN: float64 [3][n][h w] = S, ox, oy, then
+ *   float32 [n][h w] = m.  One launch.
+ * ofl_flow_local_match_grad_f32: with the workspace of the forward of the same operands and the upstream gradient grad_out fp32
+ *   [n][2][h w] = (g_x, g_y), G = -flow_sign (double)g:  w = exp((double)s - (double)m) / S,
+ *   ds = (float)(w * ((G_x * ((double)dx - ox)) + (G_y * ((double)dy - oy)))),  dss = ds / sqrtf((float)C), exactly +0 (selected) at a
+ *   position outside the frame.  `scratch` fp32 [n][(2 radius + 1)^2][h w], every element WRITTEN by a first launch (dss per offset);
+ *     grad_feat   (NULL: not made) fp32 [n][C][h w], every element WRITTEN: sum over o ascending, from +0, of dss(p, o) * W'_c(p + o)
+ *     grad_warped (NULL: not made) fp32 [n][C][h w], every element WRITTEN: usable(q) ? sum over o ascending, from +0, of
+ *                 dss(q - o, o) * feat_c(q - o), q - o inside the frame : +0 -- the gradient with respect to the sample W, which the
+ *                 backward of the warp (ofl_flow_cost_volume_chain_f32, ofl_warp_bwd_grad_f32, ofl_flow_cost_volume_gate_f32) turns into
+ *                 those of `other` and of the warp's part of the flow; the flow's own term is grad_out itself
+ *   float32 products and one float32 sum per element, no atomics; one launch per gradient after the first.
+ *
+ * OFL_E_ARG, before any launch, for: n outside 1 .. 65535, h or w < 2, h * w >= 2^31, C < 1, a radius outside 1 .. 4, a flow_sign other
+ * than +-1, a NULL required pointer, neither gradient, a negative stride, a pointer not aligned to its element (the workspace: to 8).
+ */
+int ofl_flow_local_match_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs, const float* feat,
+                             int64_t feat_bs, const float* other, int64_t other_bs, int32_t channels, float flow_sign, int32_t radius,
+                             float* out, float* prob, void* workspace, int32_t n, int32_t h, int32_t w, void* stream);
+int ofl_flow_local_match_grad_f32(const void* flow, int64_t flow_bs, int32_t flow_half, const uint8_t* mask, int64_t mask_bs,
+                                  const float* feat, int64_t feat_bs, const float* other, int64_t other_bs, int32_t channels,
+                                  float flow_sign, int32_t radius, const void* workspace, const float* grad_out, float* scratch,
+                                  float* grad_feat, float* grad_warped, int32_t n, int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ implemented (`once_differentiable` raises).
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _census, _corr_lookup, _cost_volume, _matching, _native, _photometric, _propagate, _smoothness, _ssim, _upsample
+from . import _census, _corr_lookup, _cost_volume, _local_match, _matching, _native, _photometric, _propagate, _smoothness, _ssim, _upsample
 
 
 def _reduce_to(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
@@ -447,3 +447,49 @@ class PropagateFn(torch.autograd.Function):
         like = lambda grad, t: _reduce_to(grad, t[None])[0] if t.dim() == 3 else _reduce_to(grad, t)      # C-H-W: summed over the batch
         return (_reduce_to(d_vecs, vecs) if need_vecs else None, None, like(d_query, query) if need_query else None,
                 like(d_key, key) if need_key else None, None)
+
+
+class LocalMatchFn(torch.autograd.Function):
+    """flow'(p) = flow(p) - flow_sign * E[o] under softmax_o(feat(p) . W'(p + o) / sqrt(C)) over the positions of the (2 radius + 1)^2
+    window of p that lie inside the frame, W' being `other` sampled where the flow points and +0 where the pixel is not usable, and the
+    weight 1 / S of the best position (or None): the local matching of GMFlow's refinement (Flow.match_local); params:
+    flow_sign, radius, want_prob.  Differentiable with respect to the vectors, `feat` and `other`, not the mask and not through the
+    probability: the gradient kernels give d feat and d W (gathers, bitwise reproducible), and the backward of the cost volume's warp
+    (`flow_cost_volume_chain`, `_native.warp_bwd_grad`, `flow_cost_volume_gate`) turns d W into d other and the warp's part of d flow
+    -- launches that are not made when neither is needed; d flow is the upstream gradient plus that part, one float32 addition, the
+    upstream gradient itself wherever the pixel is not usable.  The binding is looked up by name at every call: the host tests replace
+    `_local_match.flow_*` with fakes after this class exists."""
+
+    @staticmethod
+    def forward(ctx, vecs, mask, feat, other, flow_sign, radius, want_prob):
+        out, prob, stats = _local_match.flow_local_match(vecs.detach(), mask, feat.detach(), other.detach(), flow_sign, radius, want_prob,
+                                                         True)
+        ctx.save_for_backward(vecs, mask, feat, other, stats)
+        ctx.params = (flow_sign, radius)
+        if prob is not None:
+            ctx.mark_non_differentiable(prob)
+        return out, prob
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_prob=None):
+        vecs, mask, feat, other, stats = ctx.saved_tensors
+        flow_sign, radius = ctx.params
+        need_flow, _, need_feat, need_other = ctx.needs_input_grad[:4]
+        need_warped = need_flow or need_other
+        g_feat = g_other = g_flow = None
+        if need_feat or need_warped:
+            g_feat, g_warped = _local_match.flow_local_match_grad(vecs.detach(), mask, feat.detach(), other.detach(), flow_sign, radius,
+                                                                  stats, g, want_feat=bool(need_feat), want_warped=bool(need_warped))
+        if need_warped:
+            # the rule of 3.24, through its own launches (CostVolumeFn.backward)
+            src = other.detach()
+            chain = _cost_volume.flow_cost_volume_chain(vecs.detach(), flow_sign)
+            g_other, g_flow = _native.warp_bwd_grad(chain, src[None] if src.dim() == 3 else src, g_warped, flow_sign=flow_sign,
+                                                    want_src=bool(need_other), want_flow=bool(need_flow))
+            if need_flow:
+                g_flow = _cost_volume.flow_cost_volume_gate(vecs.detach(), mask, flow_sign, g_flow)
+                g_flow = g.to(g_flow.device, torch.float32) + g_flow                        # the identity term first: g + (the warp's part)
+        like = lambda grad, t: _reduce_to(grad, t[None])[0] if t.dim() == 3 else _reduce_to(grad, t)      # C-H-W: summed over the batch
+        return (_reduce_to(g_flow, vecs) if need_flow else None, None, like(g_feat, feat) if need_feat else None,
+                like(g_other, other) if need_other else None, None, None, None)

@@ -48,7 +48,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_flow_upsample_convex_f32", "ofl_flow_upsample_convex_grad_f32",                                  # (_upsample.py)
             "ofl_flow_global_match_f32", "ofl_flow_global_match_grad_f32",                                        # (_matching.py)
             "ofl_flow_propagate_global_f32", "ofl_flow_propagate_global_grad_f32",                                # (_propagate.py)
-            "ofl_flow_propagate_local_f32", "ofl_flow_propagate_local_grad_f32")
+            "ofl_flow_propagate_local_f32", "ofl_flow_propagate_local_grad_f32", "ofl_flow_local_match_f32",
+            "ofl_flow_local_match_grad_f32")
 _lib = None
 _load_lock = threading.RLock()
 

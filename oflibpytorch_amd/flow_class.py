@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import (_census, _consistency, _corr_lookup, _cost_volume, _matching, _native, _photometric, _propagate, _smoothness, _ssim,
+from . import (_census, _consistency, _corr_lookup, _cost_volume, _local_match, _matching, _native, _photometric, _propagate, _smoothness, _ssim,
                _upsample, distributed)
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
@@ -1926,6 +1926,68 @@ class Flow(object):
         feats = [(ft if ft.device == self._device else ft.to(self._device)).contiguous() for ft in feats]      # (they keep their grad_fn)
         out, out_mask = _propagate.propagate(self._fv, (self._mask if consider_mask else None), feats[0], feats[1], radius)
         return Flow(out, self._ref, out_mask, device=self._device)
+
+    def match_local(self, feat, other, radius: int = None, consider_mask: bool = None, return_prob: bool = None):
+        """The local matching of the refinement stage of GMFlow and UniMatch, as at 1/4 scale: the features `other` of the frame this
+        flow points into are warped by the flow, every pixel p of `feat` -- the features on the flow's own grid -- is correlated with
+        the (2 `radius` + 1)^2 window of the warped features around it, the softmax of feat(p) . W'(p + o) / sqrt(C) over the window
+        gives the expected offset E[o], and the vector at p becomes flow(p) + E[o] for an 's' flow, flow(p) - E[o] for a 't' flow
+        (whose sample position is p - flow(p)).  `feat` and `other` are float32 tensors or arrays, C-H-W (one image for the whole
+        batch) or N-C-H-W, with this flow's H-W and the same C >= 1; `radius` is 1, 2, 3 or 4 (default 4: 81 offsets).  The warp is
+        that of :meth:`cost_volume`: a pixel is USABLE where it is valid in this flow's mask (with `consider_mask` False: everywhere)
+        and its sample's taps lie in the frame, and the warped value W' is the sample where the pixel is usable and 0 elsewhere.  A
+        window position OUTSIDE the frame takes no part in the softmax (GMFlow's rule); one inside always does, with W' = 0 if it is
+        not usable.  Returns a flow of the same shape, reference, device and mask; with `return_prob` True a tuple of that flow and the
+        softmax weight of the best position of every pixel, float32 N-H-W.  One launch of ofl_local_match.hip from LDS tiles: the
+        warped tensor and the D planes of the volume are never written, the softmax runs in float64 in a fixed order (bitwise
+        reproducible, independent of the batch), nothing is read back to the host.  Differentiable with respect to
+        `feat`, `other` and the flow vectors (not the mask, not through the probability): the gradients of `feat` and of the warped
+        tensor are gathers without atomics, those of `other` and of the warp's part of the vectors follow from the latter through the
+        backward of :meth:`cost_volume`'s warp, with that backward's own properties; pass a flow with detached vectors for GMFlow's
+        detached warp.  The 1-D stereo variant, another
+        temperature, the full match probability, 16-bit and channels_last features and a double backward are not supported."""
+        err = "Error matching flow locally: "
+        feats = []
+        for name, ft in (("Feat", feat), ("Other", other)):
+            if isinstance(ft, np.ndarray):
+                if ft.dtype != np.float32:
+                    raise TypeError(err + name + " needs to be of dtype float32")
+                ft = torch.from_numpy(ft)
+            if not isinstance(ft, torch.Tensor):
+                raise TypeError(err + name + " needs to be a torch tensor or a numpy array")
+            if ft.dtype != torch.float32:
+                raise TypeError(err + name + " needs to be of dtype float32")
+            feats.append(ft)
+        for name, ft in zip(("Feat", "Other"), feats):
+            if ft.dim() not in (3, 4):
+                raise ValueError(err + name + " needs to have 3 or 4 dimensions, C-H-W or N-C-H-W")
+            if ft.shape[-3] < 1:
+                raise ValueError(err + name + " needs to have at least 1 channel")
+        if feats[0].shape[-3] != feats[1].shape[-3]:
+            raise ValueError(err + "Feat and other need to have the same number of channels")
+        for name, ft in zip(("Feat", "Other"), feats):
+            if tuple(ft.shape[-2:]) != tuple(self.shape[1:]):
+                raise ValueError(err + name + " needs to have the H-W shape of the flow")
+            if ft.dim() == 4 and ft.shape[0] != self.shape[0]:
+                raise ValueError(err + name + " needs to have the batch size of the flow")
+        if self.shape[1] < 2 or self.shape[2] < 2:
+            raise ValueError(err + "Flow field needs to be at least 2 pixels high and wide")
+        radius = _local_match.RADIUS if radius is None else radius
+        if not isinstance(radius, int) or isinstance(radius, bool):
+            raise TypeError(err + "Radius needs to be an integer")
+        if not 1 <= radius <= _local_match.MAX_RADIUS:
+            raise ValueError(err + "Radius needs to be 1, 2, 3 or 4")
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError(err + "Consider_mask needs to be boolean")
+        return_prob = False if return_prob is None else return_prob
+        if not isinstance(return_prob, bool):
+            raise TypeError(err + "Return_prob needs to be boolean")
+        feats = [(ft if ft.device == self._device else ft.to(self._device)).contiguous() for ft in feats]      # (they keep their grad_fn)
+        out, prob = _local_match.local_match(self._fv, (self._mask if consider_mask else None), feats[0], feats[1],
+                                             -1.0 if self._ref == 's' else 1.0, radius, return_prob)
+        flow = Flow(out, self._ref, self._mask, device=self._device)
+        return (flow, prob.to(self._device)) if return_prob else flow
 
     # ------------------------------------------------------------------------------------------
     # composition (flow_class.py:1648-1810)

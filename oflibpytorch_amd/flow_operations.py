@@ -219,6 +219,21 @@ def propagate_flow(flow, query, key=None, radius: int = None, mask=None):
     return v, (res.mask if len(flow.shape) > 3 else res.mask.squeeze(0))
 
 
+def local_matching_flow(flow, feat, other, ref: str, radius: int = None, mask=None, return_prob: bool = None):
+    """Flow(flow, ref, mask).match_local(feat, other, radius).vecs: the vectors `flow` (2-H-W or N-2-H-W, tensor or array) refined by
+    local matching between the float32 features `feat` on the flow's grid and the features `other` of the frame it points into, warped by
+    the flow -- GMFlow's softmax over the (2 radius + 1)^2 window of the warped features, the positions outside the frame excluded, and
+    the expected offset added to the flow -- float32 N-2-H-W (2-H-W for 3-D input), differentiable with respect to tensor `flow`,
+    `feat` and `other`.  With `return_prob` True a tuple of the vectors and the weight of the best position, N-H-W (H-W for 3-D
+    input).  An extension: the reference has no such function."""
+    res = Flow(flow, ref, mask).match_local(feat, other, radius=radius, return_prob=return_prob)
+    out, prob = res if isinstance(res, tuple) else (res, None)
+    v = out.vecs if len(flow.shape) > 3 else out.vecs.squeeze(0)
+    if prob is None:
+        return v
+    return v, (prob if len(flow.shape) > 3 else prob.squeeze(0))
+
+
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
     """Concatenate flow objects of equal H, W, ref and device along the batch axis (flow_operations.py:458-483)"""
     if not isinstance(flows, (list, tuple)):
