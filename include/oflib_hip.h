@@ -1372,6 +1372,57 @@ int ofl_flow_local_match_grad_f32(const void* flow, int64_t flow_bs, int32_t flo
                                   float flow_sign, int32_t radius, const void* workspace, const float* grad_out, float* scratch,
                                   float* grad_feat, float* grad_warped, int32_t n, int32_t h, int32_t w, void* stream);
 
+/*
+ * The sequence loss of RAFT, GMA, CRAFT, GMFlow, UniMatch and FlowFormer: the T refinement outputs of a network scored against ONE ground
+ * truth in one pass (which defines the numbers; ofl_sequence_loss.hip): Flow.sequence_loss / sequence_stats.  An
+ * extension: the reference has no such function.  preds / pred_bs / pred_half: HOST arrays of t entries, 1 <= t <= OFL_SEQUENCE_LOSS_MAX_T
+ * -- the device pointer of prediction i, [*,2,h,w] fp32 (half 0) or fp16 (1: up-converted in registers, exact), and the elements between
+ * its images; they are copied into the kernel arguments, nothing is uploaded.  gt likewise one flow, gt_mask (NULL: all True) bytes
+ * [*,h,w].  Per pixel, every step fp32 with one rounding per operation, both roots correctly rounded:
+ *   valid  = gt_mask and sqrt(ug ug + vg vg) < max_flow: a float compare, which a NaN or infinite magnitude (a square that overflows
+ *            included) fails; max_flow > 0, +inf allowed.  The predictions carry no mask
+ *   e_i    = sqrt(du du + dv dv), du = u_i - ug, dv = v_i - vg
+ *   t_i    = fabsf(du) + fabsf(dv) (penalty OFL_SEQUENCE_LOSS_L1) or e_i (OFL_SEQUENCE_LOSS_L2)
+ *
+ * ofl_flow_sequence_loss_workspace_bytes(t, n, h, w): bytes of the workspace of ofl_flow_sequence_loss_f64 (8-byte aligned; every word
+ *   the second launch reads is written by the first: nothing to clear), or OFL_E_SHAPE.
+ *
+ * ofl_flow_sequence_loss_f64: records float64 [n, 2 t + 4], per image over its valid pixels
+ *     [0] count   [1 + i] sum t_i   [1 + t + i] sum e_i   [1 + 2 t + k] pixels with e_{t-1} < 1, 3, 5 px (k = 0, 1, 2; an fp32 compare and
+ *     STRICTLY below, as RAFT's 1px / 3px / 5px metrics: the opposite sense to the `>` of ofl_flow_error_f64's thresholds)
+ *   Counts are exact.  Sums are float64 sums of the fp32 terms in a fixed order -- a lane's pixels ascending, the lanes of a wave by a
+ *   butterfly, the waves and then the blocks of an image in index order; a block owns OFL_SEQUENCE_LOSS_CHUNK consecutive pixels, so the
+ *   order depends on h * w and t only: no float atomics, an image's record has the same bits in any batch and on any run.  A valid
+ *   pixel's NaN term makes that sum NaN; a pixel that is not valid contributes nothing whatever it holds.  Two launches:
+ *   ofl_last_kernel_name() then names flow_sequence_loss_finish_kernel.
+ *
+ * ofl_flow_sequence_loss_grad_f32: scale fp32 [n, t] DEVICE memory (upstream gradient * weight_i / divisor); grads: a HOST array of t
+ *   device pointers fp32 [n,2,h,w], NULL for a prediction that wants none (at least one must be given).  Every element of every
+ *   gradient given is WRITTEN; +0 where the pixel is not valid.  L1: +scale where d > 0, -scale where d < 0, +0 where d is 0 or NaN, d
+ *   being du or dv.  L2: the float64 quotient (scale d) / sqrt(du du + dv dv) of the fp32 differences rounded once, +0 where the fp32
+ *   du du + dv dv is not > 0.  One launch: flow_sequence_loss_grad_kernel.
+ *
+ * `normalise` (OFL_SEQUENCE_LOSS_ALL / _VALID) names the divisor the caller forms the loss and `scale` with -- 2 h w or 2 count (L1), h w
+ * or count (L2); the kernels do not divide, the code is only checked.  Before any launch: OFL_E_NULL for a NULL required pointer (an
+ * entry of preds included; grads all NULL), OFL_E_SHAPE for t outside 1 .. 32, n outside 1 .. 65535, h or w < 1, h * w >= 2^31, OFL_E_ARG
+ * for another penalty or normalise code, a max_flow that is NaN or <= 0, a storage kind other than 0 or 1, a negative stride, a pointer
+ * not aligned to its element.  64-bit element offsets throughout.
+ */
+#define OFL_SEQUENCE_LOSS_MAX_T 32
+#define OFL_SEQUENCE_LOSS_CHUNK 2048
+#define OFL_SEQUENCE_LOSS_L1 0
+#define OFL_SEQUENCE_LOSS_L2 1
+#define OFL_SEQUENCE_LOSS_ALL 0
+#define OFL_SEQUENCE_LOSS_VALID 1
+int64_t ofl_flow_sequence_loss_workspace_bytes(int32_t t, int32_t n, int32_t h, int32_t w);
+int ofl_flow_sequence_loss_f64(const void* const* preds, const int64_t* pred_bs, const int32_t* pred_half, int32_t t, const void* gt,
+                               int64_t gt_bs, int32_t gt_half, const uint8_t* gt_mask, int64_t gt_mask_bs, float max_flow, int32_t penalty,
+                               int32_t normalise, void* workspace, double* records, int32_t n, int32_t h, int32_t w, void* stream);
+int ofl_flow_sequence_loss_grad_f32(const void* const* preds, const int64_t* pred_bs, const int32_t* pred_half, int32_t t, const void* gt,
+                                    int64_t gt_bs, int32_t gt_half, const uint8_t* gt_mask, int64_t gt_mask_bs, float max_flow,
+                                    int32_t penalty, int32_t normalise, const float* scale, float* const* grads, int32_t n, int32_t h,
+                                    int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,8 @@ implemented (`once_differentiable` raises).
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _census, _corr_lookup, _cost_volume, _local_match, _matching, _native, _photometric, _propagate, _smoothness, _ssim, _upsample
+from . import (_census, _corr_lookup, _cost_volume, _local_match, _matching, _native, _photometric, _propagate, _sequence_loss, _smoothness,
+               _ssim, _upsample)
 
 
 def _reduce_to(g: torch.Tensor, like: torch.Tensor) -> torch.Tensor:
@@ -231,6 +232,34 @@ class EpeFn(torch.autograd.Function):
         g_est, g_gt = _native.flow_epe_grad(est.detach(), gt.detach(), ctx.masks[0], ctx.masks[1], scale, want_est=bool(need_est),
                                             want_gt=bool(need_gt))
         return (_reduce_to(g_est, est) if need_est else None), (_reduce_to(g_gt, gt) if need_gt else None), None, None
+
+
+class SequenceLossFn(torch.autograd.Function):
+    """loss[n] = (sum_i gamma^(T-1-i) S[n, i]) / D[n], S the sums of the penalty of T predictions against one ground truth over its valid
+    pixels (Flow.sequence_loss): fp32, rounded once from the float64 combination of the kernel's records; the predictions
+    follow the parameters as further arguments.  Differentiable with respect to the predictions that require a gradient -- one launch
+    writes all of them, the others are neither allocated nor written --, not the ground truth or the mask.  An fp16-stored prediction is
+    saved as it is stored.  The binding is looked up by name at every call: the host tests replace it."""
+
+    @staticmethod
+    def forward(ctx, gt, gt_mask, gamma, max_flow, penalty, normalise, *preds):
+        gt = gt.detach()
+        rec = _sequence_loss.flow_sequence_loss([pr.detach() for pr in preds], gt, gt_mask, max_flow, penalty, normalise)
+        ctx.save_for_backward(gt, rec, *preds)
+        ctx.params = (gt_mask, gamma, max_flow, penalty, normalise)
+        return _sequence_loss.loss_of(rec, int(gt.shape[-2]) * int(gt.shape[-1]), gamma, penalty, normalise)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        gt, rec = ctx.saved_tensors[:2]
+        preds = ctx.saved_tensors[2:]
+        gt_mask, gamma, max_flow, penalty, normalise = ctx.params
+        wants = [bool(need) for need in ctx.needs_input_grad[6:]]
+        scale = _sequence_loss.scale_of(g, rec, int(gt.shape[-2]) * int(gt.shape[-1]), gamma, penalty, normalise)   # on the device
+        grads = _sequence_loss.flow_sequence_loss_grad([pr.detach() for pr in preds], gt, gt_mask, max_flow, penalty, normalise, scale,
+                                                       wants)
+        return (None,) * 6 + tuple(None if grad is None else _reduce_to(grad, pr) for grad, pr in zip(grads, preds))
 
 
 class SmoothnessFn(torch.autograd.Function):

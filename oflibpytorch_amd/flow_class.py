@@ -20,8 +20,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import (_census, _consistency, _corr_lookup, _cost_volume, _local_match, _matching, _native, _photometric, _propagate, _smoothness, _ssim,
-               _upsample, distributed)
+from . import (_census, _consistency, _corr_lookup, _cost_volume, _local_match, _matching, _native, _photometric, _propagate, _sequence_loss,
+               _smoothness, _ssim, _upsample, distributed)
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
                     apply_flow, _flags_to_host, _host_flags, _griddata_unavailable, track_pts, get_half_flow_outputs,
@@ -1283,6 +1283,62 @@ class Flow(object):
         vectors of either flow -- the supervised loss of a flow network; an element without a valid pixel has gradient 0."""
         gt, mask, gt_mask = self._error_operands(gt, consider_mask)
         return _native.flow_epe(self._fv, gt._fv, mask, gt_mask).to(self._device)
+
+    # ------------------------------------------------------------------------------------------
+    # the sequence loss of a refinement network (DESIGN.md 3.30; an extension: the reference has no such methods)
+    # ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _sequence_operands(preds, gt, gamma, max_flow, penalty, normalise, consider_mask):
+        """The checks the two sequence methods share; returns the arguments of `_sequence_loss.sequence_loss` and the device of the
+        result."""
+        err = _sequence_loss.ERR
+        if not isinstance(preds, (list, tuple)) or not all(isinstance(f, Flow) for f in preds):
+            raise TypeError(err + "Preds needs to be a list or a tuple of flow objects")
+        if not isinstance(gt, Flow):
+            raise TypeError(err + "Gt needs to be of type 'Flow'")
+        _sequence_loss.check_count(len(preds))
+        if any(f.shape != gt.shape for f in preds):
+            raise ValueError(err + "Flow fields need to have the same shape, including batch size")
+        if any(f.ref != gt.ref for f in preds):
+            raise ValueError(err + "Flow fields need to have the same reference")
+        gamma, max_flow, penalty, normalise = _sequence_loss.check_params(gamma, max_flow, penalty, normalise)
+        consider_mask = True if consider_mask is None else consider_mask
+        if not isinstance(consider_mask, bool):
+            raise TypeError(err + "Consider_mask needs to be boolean")
+        dev = preds[0]._device
+        if gt._device != dev:
+            gt = gt.to_device(dev)
+        return ([f._fv for f in preds], gt._fv, gt._mask if consider_mask else None, gamma, max_flow, penalty, normalise), dev
+
+    @staticmethod
+    def sequence_loss(preds: Union[list, tuple], gt: FlowAlias, gamma: float = None, max_flow: float = None, penalty: str = None,
+                      normalise: str = None, consider_mask: bool = None) -> torch.Tensor:
+        """The sequence loss of RAFT, GMA, CRAFT, GMFlow, UniMatch and FlowFormer per batch element, float32 [N] on the device of the
+        first prediction: `preds` is a list or tuple of the 1 to 32 refinement outputs of a network, flows of the shape and reference
+        of the ground truth `gt`, and loss_n = sum_i gamma^(T-1-i) * mean_i, the last prediction weighing 1 (`gamma` default 0.8).  A
+        pixel is VALID where `gt.mask` is True (with `consider_mask` False: everywhere) and the magnitude of the ground truth is
+        below `max_flow` (default 400, inf allowed; a NaN or infinite ground truth is never valid).  The masks of the predictions
+        are NOT read: the outputs of a network carry none, and T masks would give T different counts.  `penalty` 'l1' (default)
+        sums |du| + |dv| over the valid pixels, 'l2' the end-point error; `normalise` 'all' (default, RAFT's) divides by all 2 H W
+        ('l2': H W) terms of the image, 'valid' by those of the valid pixels (NaN for an element without one, whose gradient is
+        0).  `loss.mean()` under ('l1', 'all') is RAFT's scalar.  One pass of ofl_sequence_loss.hip reads the ground truth and its mask
+        once for all T predictions; float64 sums in a fixed order (bitwise reproducible, independent of the batch; DESIGN.md 3.30);
+        nothing is read back to the host.  Differentiable with respect to the vectors of the predictions that require a gradient --
+        one more launch writes all of them -- not the ground truth or any mask."""
+        args, dev = Flow._sequence_operands(preds, gt, gamma, max_flow, penalty, normalise, consider_mask)
+        return _sequence_loss.sequence_loss(*args).to(dev)
+
+    @staticmethod
+    def sequence_stats(preds: Union[list, tuple], gt: FlowAlias, gamma: float = None, max_flow: float = None, penalty: str = None,
+                       normalise: str = None, consider_mask: bool = None) -> dict:
+        """What :meth:`sequence_loss` is made of, from the same pass, as a dict of tensors on the device of the first prediction:
+        'count' int64 [N], the valid pixels; 'loss' float32 [N]; 'weights' float64 [T]; 'terms' float64 [N,T], the mean penalty of
+        every prediction (loss = sum_i weights_i terms_i); 'epe' float64 [N,T], the mean end-point error of every prediction over the
+        valid pixels (NaN where count is 0) -- the convergence curve over the iterations; 'within' float64 [N,3], the share of valid
+        pixels whose end-point error of the LAST prediction is below (strictly, unlike the `>` of :meth:`error_stats`) 1, 3 and 5
+        px, RAFT's 1px / 3px / 5px metrics.  The masks of the predictions are not read.  Not differentiable."""
+        args, dev = Flow._sequence_operands(preds, gt, gamma, max_flow, penalty, normalise, consider_mask)
+        return {k: v.to(dev) for k, v in _sequence_loss.sequence_stats(*args).items()}
 
     # ------------------------------------------------------------------------------------------
     # forward-backward consistency (DESIGN.md 3.18; an extension: the reference has no such methods)

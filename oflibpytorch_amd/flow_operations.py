@@ -5,6 +5,7 @@ from typing import Union
 import numpy as np
 import torch
 
+from . import _sequence_loss
 from ._corr_lookup import corr_pyramid  # noqa: F401  (exported by the package)
 from .flow_class import Flow
 from .utils import get_valid_ref
@@ -232,6 +233,38 @@ def local_matching_flow(flow, feat, other, ref: str, radius: int = None, mask=No
     if prob is None:
         return v
     return v, (prob if len(flow.shape) > 3 else prob.squeeze(0))
+
+
+def flow_sequence_loss(flows, gt, gt_mask=None, gamma: float = None, max_flow: float = None, penalty: str = None,
+                       normalise: str = None) -> torch.Tensor:
+    """Flow.sequence_loss for the raw outputs of a network: `flows` is a list or tuple of 1 to 32 float32 or float16 tensors 2-H-W or
+    N-2-H-W, or ONE stacked tensor [T,(N,)2,H,W], which is unbound along axis 0 and whose slices are used in place; `gt` (tensor or
+    array, with the optional mask `gt_mask`) is the ground truth of that shape.  Returns the loss, float32 [N] (a scalar tensor for 3-D
+    input) on the device of the predictions, differentiable with respect to them (the gradient of a stacked tensor has the stack's
+    shape).  The predictions are NOT validated and no flow object is made of them: T validation passes would cost more than the loss, and
+    a non-finite prediction shows up as a NaN loss.  An extension: the reference has no such function."""
+    err = _sequence_loss.ERR
+    if isinstance(flows, torch.Tensor):
+        if flows.dim() not in (4, 5):
+            raise ValueError(err + "A stacked tensor of predictions needs to have 4 or 5 dimensions, T-2-H-W or T-N-2-H-W")
+        flows = flows.unbind(0)
+    if not isinstance(flows, (list, tuple)) or not all(isinstance(f, torch.Tensor) for f in flows):
+        raise TypeError(err + "Flows needs to be a list or a tuple of tensors, or one stacked tensor")
+    _sequence_loss.check_count(len(flows))
+    if any(f.dtype not in (torch.float32, torch.float16) for f in flows):
+        raise TypeError(err + "Flows need to be of dtype float32 or float16")
+    if flows[0].dim() not in (3, 4) or flows[0].shape[-3] != 2 or min(flows[0].shape) < 1:
+        raise ValueError(err + "Flows need to be of shape 2-H-W or N-2-H-W")
+    if any(f.shape != flows[0].shape for f in flows):
+        raise ValueError(err + "Flows need to have the same shape, including batch size")
+    gamma, max_flow, penalty, normalise = _sequence_loss.check_params(gamma, max_flow, penalty, normalise)
+    batched = flows[0].dim() == 4
+    truth = Flow(gt, 't', gt_mask)
+    if (truth.shape[0],) + tuple(truth.shape[1:]) != ((flows[0].shape[0] if batched else 1),) + tuple(flows[0].shape[-2:]):
+        raise ValueError(err + "Gt needs to have the shape of the flows, including batch size")
+    preds = [f if batched else f[None] for f in flows]
+    loss = _sequence_loss.sequence_loss(preds, truth._fv, truth._mask, gamma, max_flow, penalty, normalise).to(flows[0].device)
+    return loss if batched else loss.squeeze(0)
 
 
 def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
