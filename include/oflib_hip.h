@@ -1423,6 +1423,38 @@ int ofl_flow_sequence_loss_grad_f32(const void* const* preds, const int64_t* pre
                                     int32_t penalty, int32_t normalise, const float* scale, float* const* grads, int32_t n, int32_t h,
                                     int32_t w, void* stream);
 
+/*
+ * The composition of a clip's frame-to-frame flows f_1 .. f_t into the flow from the first frame to the last, in one launch (DESIGN.md
+ * 3.31, which defines the numbers; ofl_chain.hip): Flow.chain / chain_flows.  An extension: the reference composes two flows at a time
+ * (combine_with mode 3), of which this is the fold without the intermediate flows.  flows / flow_bs / flow_half / masks / mask_bs: HOST
+ * arrays of t entries in the order of TIME, 2 <= t <= OFL_CHAIN_MAX_T -- the device pointer of flow k, [*,2,h,w] fp32 (half 0) or fp16
+ * (1: up-converted in registers, exact), the elements between its images (0 broadcasts one image), its mask [*,h,w] bytes (any non-zero
+ * byte is True; a NULL entry, or masks == NULL for all of them, is all True and no byte is read for it) and the bytes between the
+ * mask's images; they are copied into the kernel arguments, nothing is uploaded.  Inputs are never written.
+ *
+ * Per pixel p, an independent walk, every step fp32 with one rounding per operation:
+ *   flow_sign -1 ('s' flows, result on the first frame's grid): acc = f_1(p), m = mask_1(p); for k = 2 .. t the position is p + acc
+ *   flow_sign +1 ('t' flows, result on the last frame's grid):  acc = f_t(p), m = mask_t(p); for k = t - 1 .. 1 the position is p - acc
+ *   step k: the four taps and weights of the backward warp at that position (ofl_warp_bwd_f32); (bu, bv) the sample of f_k, a tap outside
+ *   the frame reading 0, `v_nw * nw` then three fmaf in the order ne, sw, se; mr the same chain over the taps' validity (inside the
+ *   frame and True in mask_k); then acc = acc + (bu, bv), two plain adds, and m = m and (mr > 0.99999f).
+ * The vectors are accumulated whatever m says, positions outside the frame included; a non-finite position fails every comparison, its
+ * taps read 0 and m turns false.  These are the bits of the fold of combine_with mode 3 (ofl_warp_bwd_f32 with the addend) where that
+ * fold takes none of its early exits.
+ *
+ *   out, out_mask   want_all == 0: fp32 [n,2,h,w] and uint8 [n,h,w], the whole chain.  want_all == 1: fp32 [t-1,n,2,h,w] and uint8
+ *                   [t-1,n,h,w], every partial chain of two flows and more as the walk passes it: flow_sign -1, slot j holds the chain
+ *                   of f_1 .. f_{j+2}; flow_sign +1, slot j holds the chain of f_{j+1} .. f_t (the whole chain: slot t - 2 and slot 0).
+ *   Every element of both outputs is WRITTEN (vectors under a false mask included; nothing to clear beforehand); mask bytes are 0 / 1.
+ * OFL_E_ARG, before any launch, for: t outside 2 .. 32, n outside 1 .. 65535, h or w < 2, h * w >= 2^31, a flow_sign other than +-1, a
+ * want_all or storage kind other than 0 or 1, a NULL flows, flow_bs or flow_half array (mask_bs with masks given), a NULL flow or output,
+ * a negative stride, a pointer not aligned to its element.  One launch: flow_chain_kernel.  64-bit element offsets throughout.
+ */
+#define OFL_CHAIN_MAX_T 32
+int ofl_flow_chain_f32(const void* const* flows, const int64_t* flow_bs, const int32_t* flow_half, const uint8_t* const* masks,
+                       const int64_t* mask_bs, int32_t t, float flow_sign, float* out, uint8_t* out_mask, int32_t want_all, int32_t n,
+                       int32_t h, int32_t w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

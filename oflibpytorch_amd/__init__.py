@@ -41,7 +41,10 @@ feat(p) . W'(p + o) / sqrt(C) with the positions outside the frame excluded, and
 without the warped tensor or the volume -- differentiable with respect to both feature tensors and the vectors (not in
 the reference).  `Flow.sequence_loss` / `sequence_stats` and `flow_sequence_loss` give the objective all of these networks train on --
 the gamma-weighted sum over the T refinement outputs of the masked L1 (or end-point) distance to one ground truth, which is read once
-for all T -- differentiable with respect to the predictions (not in the reference).  No CPU fallback: see
+for all T -- differentiable with respect to the predictions (not in the reference).  `Flow.chain` and `chain_flows` compose the 1 to
+32 frame-to-frame flows of a clip into the flow from its first frame to its last -- the fold of `combine_with` mode 3, bit for bit where that fold takes no early
+exit, as one walk per pixel in one launch, with every partial chain (the dense trajectories) on request (not in the reference).  No
+CPU fallback: see
 `_native.NativeUnavailable`.
 """
 from .flow_class import Flow, set_revalidate_every_call, get_revalidate_every_call
@@ -50,7 +53,7 @@ from .flow_operations import (combine_flows, switch_flow_ref, invert_flow, valid
                               flow_error_stats, flow_epe, flow_consistency, flow_smoothness, flow_smoothness_stats,
                               flow_photometric, flow_photometric_stats, flow_census, flow_census_stats,
                               flow_ssim, flow_ssim_stats, flow_cost_volume, flow_corr_lookup, corr_pyramid, upsample_flow_convex,
-                              global_matching_flow, propagate_flow, local_matching_flow, flow_sequence_loss)
+                              global_matching_flow, propagate_flow, local_matching_flow, flow_sequence_loss, chain_flows)
 from .utils import (from_matrix, from_transforms, load_kitti, load_sintel, load_sintel_mask, resize_flow, apply_flow, is_zero_flow, get_pure_pytorch,
                     set_pure_pytorch, unset_pure_pytorch, to_numpy, to_tensor, move_axis, apply_s_flow,
                     grid_from_unstructured_data, get_flow_endpoints, threshold_vectors, normalise_coords, track_pts,

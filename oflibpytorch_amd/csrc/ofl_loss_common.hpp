@@ -1,5 +1,5 @@
 // ofl_loss_common.hpp -- what the fused metric and loss sources share (ofl_metrics.hip, ofl_consistency.hip, ofl_smoothness.hip,
-// ofl_photometric.hip, ofl_census.hip, ofl_ssim.hip, ofl_cost_volume.hip, ofl_corr_lookup.hip, ofl_upsample.hip, ofl_sequence_loss.hip): the launch recorder, the bilinear sample of the backward warp
+// ofl_photometric.hip, ofl_census.hip, ofl_ssim.hip, ofl_cost_volume.hip, ofl_corr_lookup.hip, ofl_upsample.hip, ofl_sequence_loss.hip, ofl_chain.hip): the launch recorder, the bilinear sample of the backward warp
 // and its derivative, the per-block record sums and their finish, the host checks.  Internal: not part of the C ABI
 // (include/oflib_hip.h).  Every geometry constant (kThreads, kRec, tile and block limits) stays in the including source and comes in as a
 // template argument; a source pulls `ofl_loss` into its anonymous namespace.

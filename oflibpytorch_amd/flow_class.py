@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import (_census, _consistency, _corr_lookup, _cost_volume, _local_match, _matching, _native, _photometric, _propagate, _sequence_loss,
+from . import (_census, _chain, _consistency, _corr_lookup, _cost_volume, _local_match, _matching, _native, _photometric, _propagate, _sequence_loss,
                _smoothness, _ssim, _upsample, distributed)
 from .utils import (get_valid_vecs, get_valid_ref, get_valid_mask, get_valid_device, get_valid_padding,
                     get_valid_shape, get_pure_pytorch, move_axis, from_matrix, from_transforms, resize_flow,
@@ -1339,6 +1339,66 @@ class Flow(object):
         px, RAFT's 1px / 3px / 5px metrics.  The masks of the predictions are not read.  Not differentiable."""
         args, dev = Flow._sequence_operands(preds, gt, gamma, max_flow, penalty, normalise, consider_mask)
         return {k: v.to(dev) for k, v in _sequence_loss.sequence_stats(*args).items()}
+
+    # ------------------------------------------------------------------------------------------
+    # the composition of a clip's flows (DESIGN.md 3.31; an extension: the reference composes two flows at a time)
+    # ------------------------------------------------------------------------------------------
+    @staticmethod
+    def chain(flows: Union[list, tuple], return_all: bool = None) -> Union[FlowAlias, list]:
+        """The flow from the first frame of a clip to its last, composed from the 1 to 32 frame-to-frame flows `flows`, a list or
+        tuple ordered in time (`flows[k]` runs from frame k to frame k + 1) of flows of one shape and one reference.  For 's' flows
+        the result lives on the grid of frame 0 and is the left fold `(((f_1 (+) f_2) (+) f_3) ...)` of :meth:`combine_with` mode 3; for
+        't' flows it lives on the grid of the last frame and is the right fold `(f_1 (+) (... (f_{T-1} (+) f_T)))`.  The vectors and the
+        mask carry the bits of that fold wherever the fold takes none of its early exits (an operand that is all zero under its mask,
+        an accumulated flow under the threshold of :meth:`apply`); where it would, the general formula is the definition (DESIGN.md
+        3.31): the vectors agree, the mask is the one the sampling gives.  One launch of ofl_chain.hip whatever T is: every pixel walks
+        through the flows with its running vector and mask bit in registers, no intermediate flow is written, read back, wrapped or
+        validated.  With `return_all` True a list of T flows: for 's' flows `out[k]` is the chain of `flows[:k + 1]` -- the dense
+        trajectories of the pixels of frame 0, the whole chain last -- for 't' flows the chain of `flows[k:]`, the whole chain first; the
+        element that is a single input flow is that object, the others are views of one allocation the same launch writes.  A single
+        flow is returned as it is.  The result is on the device of the first flow.  When autograd is recording and the vectors of a
+        flow require a gradient, the call runs the fold of :meth:`combine_with` instead and keeps its gradients: the fused kernel has
+        no backward."""
+        err = _chain.ERR
+        if not isinstance(flows, (list, tuple)) or not all(isinstance(f, Flow) for f in flows):
+            raise TypeError(err + "Flows needs to be a list or a tuple of flow objects")
+        if not 1 <= len(flows) <= _chain.MAX_T:
+            raise ValueError(err + "The sequence needs to hold 1 to {} flows".format(_chain.MAX_T))
+        first = flows[0]
+        if any(f.shape != first.shape for f in flows):
+            raise ValueError(err + "Flow fields need to have the same shape, including batch size")
+        if any(f.ref != first.ref for f in flows):
+            raise ValueError(err + "Flow fields need to have the same reference: switch_ref the others")
+        if first.shape[1] < 2 or first.shape[2] < 2:
+            raise ValueError(err + "Flow fields need to be at least 2 pixels high and wide")
+        return_all = False if return_all is None else return_all
+        if not isinstance(return_all, bool):
+            raise TypeError(err + "Return_all needs to be boolean")
+        t, ref, dev = len(flows), first._ref, first._device
+        if t == 1:
+            return [first] if return_all else first
+        flows = [f if f._device == dev else f.to_device(dev) for f in flows]
+        if _native._wants_grad(*[f._fv for f in flows]):
+            return Flow._chain_fold(flows, return_all)
+        vecs, mask = _chain.flow_chain([f._fv.detach() for f in flows], [f._mask for f in flows], -1.0 if ref == 's' else 1.0, return_all)
+        if not return_all:
+            return Flow._wrap(vecs, ref, mask, dev, fresh=True)
+        parts = [Flow._wrap(vecs[j], ref, mask[j], dev, fresh=True) for j in range(t - 1)]
+        return [flows[0]] + parts if ref == 's' else parts + [flows[-1]]
+
+    @staticmethod
+    def _chain_fold(flows: list, return_all: bool) -> Union[FlowAlias, list]:
+        """:meth:`chain` as the fold of :meth:`combine_with` mode 3 it is defined by -- T - 1 launches, early exits included: the route
+        of flows whose vectors require a gradient."""
+        if flows[0]._ref == 's':
+            out = [flows[0]]
+            for f in flows[1:]:
+                out.append(out[-1].combine_with(f, 3))
+            return out if return_all else out[-1]
+        out = [flows[-1]]
+        for f in reversed(flows[:-1]):
+            out.insert(0, f.combine_with(out[0], 3))
+        return out if return_all else out[0]
 
     # ------------------------------------------------------------------------------------------
     # forward-backward consistency (DESIGN.md 3.18; an extension: the reference has no such methods)

@@ -5,7 +5,7 @@ from typing import Union
 import numpy as np
 import torch
 
-from . import _sequence_loss
+from . import _chain, _sequence_loss
 from ._corr_lookup import corr_pyramid  # noqa: F401  (exported by the package)
 from .flow_class import Flow
 from .utils import get_valid_ref
@@ -280,3 +280,30 @@ def batch_flows(flows: Union[list, tuple]) -> FlowAlias:
     if len({str(f.device) for f in flows}) != 1:
         raise ValueError("Error batching flows: Flow objects need to be on the same device")
     return Flow(torch.cat([f.vecs for f in flows], dim=0), flows[0].ref, torch.cat([f.mask for f in flows], dim=0))
+
+
+def chain_flows(flows, ref: str, masks=None, return_all: bool = None):
+    """Flow.chain for arrays / tensors: `flows` is a list or tuple of 1 to 32 arrays or tensors 2-H-W or N-2-H-W of one shape, ordered in
+    time, `ref` their common reference, `masks` None or a list or tuple of as many masks (N-)H-W, of which single entries may be None.
+    Returns the vectors of the chain, float32 (N-)2-H-W, 3-D in -> 3-D out; with `masks` given a tuple of the vectors and the mask, bool
+    (N-)H-W; with `return_all` True a list of T such results (Flow.chain says which).  An extension: the reference has
+    no such function."""
+    err = _chain.ERR
+    if not isinstance(flows, (list, tuple)) or not all(isinstance(f, (np.ndarray, torch.Tensor)) for f in flows):
+        raise TypeError(err + "Flows needs to be a list or a tuple of numpy arrays or torch tensors")
+    if not 1 <= len(flows) <= _chain.MAX_T:
+        raise ValueError(err + "The sequence needs to hold 1 to {} flows".format(_chain.MAX_T))
+    if masks is not None and (not isinstance(masks, (list, tuple)) or len(masks) != len(flows)):
+        raise TypeError(err + "Masks needs to be None or a list or a tuple of one mask, or None, per flow")
+    ref = get_valid_ref(ref)
+    objs = [Flow(f, ref, None if masks is None else masks[i]) for i, f in enumerate(flows)]
+    res = Flow.chain(objs, return_all=return_all)
+    batched = len(flows[0].shape) > 3
+
+    def unwrap(r: Flow):
+        v = r.vecs if batched else r.vecs.squeeze(0)
+        if masks is None:
+            return v
+        return v, (r.mask if batched else r.mask.squeeze(0))
+
+    return [unwrap(r) for r in res] if isinstance(res, list) else unwrap(res)
