@@ -1278,6 +1278,34 @@ int ofl_flow_global_match_grad_f32(const float* feat, int64_t feat_bs, const flo
                                    float flow_sign, const void* workspace, const float* grad_out, float* grad_feat, float* grad_other,
                                    int32_t n, int32_t h, int32_t w, void* stream);
 
+/*
+ * The global matching of fp16 / bf16 features on the matrix cores (which defines the numbers; ofl_matching_x16.hip):
+ * Flow.from_matching of two tensors of one 16-bit dtype.  `feat` and `other` [*,C,h,w] elements of `elem` (OFL_X16_HALF, OFL_X16_BFLOAT,
+ * the convention of ofl_warp_bwd_x16), planes contiguous, feat_bs / other_bs elements between images (0: one image for the whole batch),
+ * C >= 1 without an upper limit (padded with zeros on both sides to a multiple of 16), h, w >= 1.  For pixel p and every position q:
+ *   s_q      = (sum over c of feat_c(p) * other_c(q)) * kInvRoot: the products exact in float32, summed in float32 by
+ *            v_mfma_f32_32x32x16_{f16,bf16} in its own order, then ONE float32 product with kInvRoot = (float)(1.0 / sqrt((double)C))
+ *   softmax  a float32 running maximum; weights exp(s_q - m) by v_exp_f32 of the float32 product with log2(e) (exactly 1 at 0, +0 below
+ *            -128); float32 sums over the 16 positions a lane holds of a chunk of 32; float64 sums across chunks with the float64 rescale
+ *            of ofl_flow_global_match_f32; a position beyond h w takes no part
+ *   result   ox = X / S, oy = Y / S; u = (float)((ox - (double)x) * -flow_sign), v alike; prob = (float)(1.0 / S), as there
+ * out fp32 [n][2][h w], every element WRITTEN; prob (NULL: not made) fp32 [n][h w], every element WRITTEN; stats (NULL: no backward will
+ * follow) 28 n h w bytes, 8-byte aligned, every byte WRITTEN, the layout and meaning of ofl_flow_global_match_f32's workspace (m the FINAL
+ * maximum): ofl_flow_global_match_grad_f32 reads it, given the exact float32 up-conversions of the features.  `workspace`:
+ * ofl_flow_global_match_x16_pack_bytes(C, n, h, w) bytes, 16-byte aligned, every byte WRITTEN by the first launch and read by the second
+ * (both tensors pixel-major, padded with zeros); its contents mean nothing afterwards.  Inputs are never written.  Two launches:
+ * ofl_last_kernel_name() then names flow_global_match_x16_kernel<half_t | bf16_t, channels stay in registers>.
+ *
+ * OFL_E_ARG, before any launch, for: n outside 1 .. 65535, h or w outside 1 .. 2^24, h * w >= 2^31, C < 1, another `elem`, a flow_sign
+ * other than +-1, a NULL feat, other, out or workspace, a negative stride, a pointer not aligned to what is loaded through it (the
+ * features: 2 bytes, out and prob: 4, stats: 8, workspace: 16).  ofl_flow_global_match_x16_pack_bytes returns OFL_E_ARG (negative) for
+ * a frame so refused.
+ */
+int64_t ofl_flow_global_match_x16_pack_bytes(int32_t channels, int32_t n, int32_t h, int32_t w);
+int ofl_flow_global_match_x16(const void* feat, int64_t feat_bs, const void* other, int64_t other_bs, int32_t channels, int32_t elem,
+                              float flow_sign, float* out, float* prob, void* stats, void* workspace, int32_t n, int32_t h, int32_t w,
+                              void* stream);
+
 /* ---- flow propagation by attention -----------------------------------------------------------------------------------------------
  * flow'(p) = sum_q softmax_q(query(p) . key(q) / sqrt(C)) flow(q), GMFlow's and UniMatch's propagation of matched vectors by
  * self-attention, over ALL positions q (global) or over the (2 radius + 1)^2 window of p with zero padding (local), without the (h w)^2

@@ -31,7 +31,9 @@ the 3 x 3 neighbourhood of k flow under the softmax of its nine predicted logits
 differentiable with respect to the logits and the vectors (not in the reference).  `Flow.from_matching` and
 `global_matching_flow` give the first flow of a matching-style network (GMFlow, UniMatch) -- for every pixel the softmax over ALL
 positions of the other frame of feat(p) . other(q) / sqrt(C), the expected position minus p, and the matching probability, streamed
-without the (H W)^2 volume -- differentiable with respect to both feature tensors (not in the reference).
+without the (H W)^2 volume -- differentiable with respect to both feature tensors (not in the reference); two float16
+or two bfloat16 feature tensors, as a network under autocast has them, are matched on the matrix cores without a float32 copy, with
+float32 results and gradients in the features' dtype.
 `Flow.propagate` and `propagate_flow` give the flow propagation by attention that follows it -- the vector at p becomes the softmax over
 all positions q, or over a zero-padded window of radius 1 to 4, of query(p) . key(q) / sqrt(C), times flow(q), with the positions the
 flow's mask excludes left out, so that matched vectors fill occluded regions -- differentiable with respect to both feature tensors and

@@ -427,11 +427,16 @@ class GlobalMatchFn(torch.autograd.Function):
     (or None), GMFlow's global matching (Flow.from_matching).  Differentiable with respect to `feat` and `other`, not
     through the probability: both gradients recompute the logits on the saved maximum and sum, every sum in a fixed order, bitwise
     reproducible.  The binding is looked up by name at every call: the host tests replace `_matching.flow_*` with fakes after this
-    class exists."""
+    class exists.
+
+    Two float16 or two bfloat16 tensors take the matrix-core forward.  The graph keeps the 16-bit tensors and the
+    statistics, no float32 copy; the backward forms the exact float32 up-conversions for the length of its call, runs the float32
+    gradient kernels on the 16-bit forward's statistics and rounds each gradient once to the features' dtype."""
 
     @staticmethod
     def forward(ctx, feat, other, flow_sign, want_prob):
-        out, prob, stats = _matching.flow_global_match(feat.detach(), other.detach(), flow_sign, want_prob, True)
+        forward = _matching.flow_global_match_x16 if feat.dtype in _matching.X16 else _matching.flow_global_match
+        out, prob, stats = forward(feat.detach(), other.detach(), flow_sign, want_prob, True)
         ctx.save_for_backward(feat, other, stats)
         ctx.flow_sign = flow_sign
         if prob is not None:
@@ -443,8 +448,9 @@ class GlobalMatchFn(torch.autograd.Function):
     def backward(ctx, g, _g_prob=None):
         feat, other, stats = ctx.saved_tensors
         need_feat, need_other = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        d_feat, d_other = _matching.flow_global_match_grad(feat.detach(), other.detach(), ctx.flow_sign, stats, g,
+        d_feat, d_other = _matching.flow_global_match_grad(feat.detach().float(), other.detach().float(), ctx.flow_sign, stats, g,
                                                            want_feat=bool(need_feat), want_other=bool(need_other))
+        # (`.float()` of a float32 tensor is that tensor; `_reduce_to` rounds a gradient once to the dtype of its operand)
         like = lambda grad, t: _reduce_to(grad, t[None])[0] if t.dim() == 3 else _reduce_to(grad, t)      # C-H-W: the batch of one
         return (like(d_feat, feat) if need_feat else None, like(d_other, other) if need_other else None, None, None)
 

@@ -15,7 +15,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ofl_kernels.hip"), os.path.join(_PKG, "cs
            os.path.join(_PKG, "csrc", "ofl_corr_lookup.hip"), os.path.join(_PKG, "csrc", "ofl_upsample.hip"),
            os.path.join(_PKG, "csrc", "ofl_matching.hip"), os.path.join(_PKG, "csrc", "ofl_propagate.hip"),
            os.path.join(_PKG, "csrc", "ofl_local_match.hip"), os.path.join(_PKG, "csrc", "ofl_sequence_loss.hip"),
-           os.path.join(_PKG, "csrc", "ofl_chain.hip"),
+           os.path.join(_PKG, "csrc", "ofl_chain.hip"), os.path.join(_PKG, "csrc", "ofl_matching_x16.hip"),
            # plain C++ host code (the PNG unfilter of the dataset loaders): no device code in it, linked into the same library
            os.path.join(_PKG, "csrc", "ofl_png_host.cpp")]
 # [0]: the C ABI; then the internal headers, which the sources include by relative path

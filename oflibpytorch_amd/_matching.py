@@ -1,8 +1,10 @@
-"""ctypes binding of the global matching (ofl_matching.hip; C ABI: include/oflib_hip.h).
+"""ctypes binding of the global matching (ofl_matching.hip, DESIGN.md 3.27, and ofl_matching_x16.hip, DESIGN.md 3.32, for two fp16 or two
+bf16 tensors; C ABI: include/oflib_hip.h).
 
-A module of its own next to `_native`, whose helpers it uses: it declares the two entry points it calls and allocates its outputs, the
-matching probability, the workspace of the backward and the gradients under its own module-level name `torch`, which the dirty-memory
-tests replace (tests/test_gpu_matching_dirty_memory.py).  Nothing is read back.
+A module of its own next to `_native`, whose helpers it uses: it declares the entry points it calls and allocates its outputs, the
+matching probability, the workspace of the backward, the packed rows of the 16-bit route and the gradients under its own module-level
+name `torch`, which the dirty-memory tests replace (tests/test_gpu_matching_dirty_memory.py, tests/test_gpu_matching_x16_dirty_memory.py).
+Nothing is read back.
 """
 import ctypes
 
@@ -11,12 +13,13 @@ import torch
 from ._native import _check, _on, _planes, _ptr, _stream, _wants_grad, device, load_library
 
 STATS_BYTES = 28              # of the workspace, per pixel: S, ox, oy float64, m float32
+X16 = {torch.float16: 0, torch.bfloat16: 1}          # OFL_X16_HALF, OFL_X16_BFLOAT (include/oflib_hip.h)
 
 _declared = None
 
 
 def _library():
-    """libofl_hip.so with the two entry points of this module declared."""
+    """libofl_hip.so with the entry points of this module declared."""
     global _declared
     lib = load_library()
     if _declared is not lib:
@@ -25,15 +28,23 @@ def _library():
         lib.ofl_flow_global_match_f32.restype = ctypes.c_int
         lib.ofl_flow_global_match_grad_f32.argtypes = [p, i64, p, i64, i32, f32, p, p, p, p, i32, i32, i32, p]
         lib.ofl_flow_global_match_grad_f32.restype = ctypes.c_int
+        lib.ofl_flow_global_match_x16.argtypes = [p, i64, p, i64, i32, i32, f32, p, p, p, p, i32, i32, i32, p]
+        lib.ofl_flow_global_match_x16.restype = ctypes.c_int
+        lib.ofl_flow_global_match_x16_pack_bytes.argtypes = [i32, i32, i32, i32]
+        lib.ofl_flow_global_match_x16_pack_bytes.restype = ctypes.c_int64
         _declared = lib
     return lib
 
 
 def check_features(feat, other):
-    """The checks every route shares: two float32 tensors of one shape, C-H-W or N-C-H-W, no empty axis."""
+    """The checks every route shares: two float32 tensors, or two tensors of ONE 16-bit dtype (float16, bfloat16), of one shape, C-H-W
+    or N-C-H-W, no empty axis."""
     for t in (feat, other):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise TypeError("oflibpytorch_amd: the feature tensors need to be float32 tensors")
+        if not isinstance(t, torch.Tensor) or (t.dtype != torch.float32 and t.dtype not in X16):
+            raise TypeError("oflibpytorch_amd: the feature tensors need to be float32 tensors, or both float16 or both bfloat16")
+    if feat.dtype != other.dtype:
+        raise TypeError("oflibpytorch_amd: the feature tensors need to be float32 tensors, or both float16 or both bfloat16, not a "
+                        "mixed pair")
     if feat.dim() not in (3, 4):
         raise ValueError("oflibpytorch_amd: the feature tensors need to be C-H-W or N-C-H-W")
     if tuple(feat.shape) != tuple(other.shape):
@@ -42,9 +53,9 @@ def check_features(feat, other):
         raise ValueError("oflibpytorch_amd: the feature tensors are empty")
 
 
-def _features(t, dev, n, what):
+def _features(t, dev, n, what, dtype=torch.float32):
     t = t.detach()
-    return _planes(t[None] if t.dim() == 3 else t, dev, torch.float32, n, what)
+    return _planes(t[None] if t.dim() == 3 else t, dev, dtype, n, what)
 
 
 def _frame(feat):
@@ -69,6 +80,32 @@ def flow_global_match(feat: torch.Tensor, other: torch.Tensor, flow_sign: float 
         _check(lib.ofl_flow_global_match_f32(_ptr(ft), fbs, _ptr(ot), obs, c, float(flow_sign), _ptr(out), _ptr(prob), _ptr(stats), n, h, w,
                                              _stream(dev)), "ofl_flow_global_match_f32")
     del ft, ot
+    return out, prob, stats
+
+
+def flow_global_match_x16(feat: torch.Tensor, other: torch.Tensor, flow_sign: float = -1.0, want_prob: bool = False, want_stats: bool = False):
+    """The global matching of two fp16 or two bf16 feature tensors on the matrix cores (ofl_flow_global_match_x16): the
+    arguments and the results of `flow_global_match` -- the vectors and the probability float32, the statistics in the same layout, so
+    that `flow_global_match_grad` reads them.  Two launches (the tensors to pixel-major rows, then the walk); the packed rows are a
+    workspace of this call; nothing is read back."""
+    check_features(feat, other)
+    if feat.dtype not in X16:
+        raise TypeError("oflibpytorch_amd: flow_global_match_x16 needs float16 or bfloat16 feature tensors")
+    lib, dev = _library(), device(feat, other)
+    n, c, h, w = _frame(feat)
+    with _on(dev):
+        ft, fbs = _features(feat, dev, n, "features", feat.dtype)
+        ot, obs = _features(other, dev, n, "other features", feat.dtype)
+        size = int(lib.ofl_flow_global_match_x16_pack_bytes(c, n, h, w))
+        if size < 0:
+            _check(size, "ofl_flow_global_match_x16_pack_bytes")
+        out = torch.empty((n, 2, h, w), dtype=torch.float32, device=dev)
+        prob = torch.empty((n, h, w), dtype=torch.float32, device=dev) if want_prob else None
+        stats = torch.empty((STATS_BYTES * n * h * w,), dtype=torch.uint8, device=dev) if want_stats else None
+        pack = torch.empty((size,), dtype=torch.uint8, device=dev)
+        _check(lib.ofl_flow_global_match_x16(_ptr(ft), fbs, _ptr(ot), obs, c, X16[feat.dtype], float(flow_sign), _ptr(out), _ptr(prob),
+                                             _ptr(stats), _ptr(pack), n, h, w, _stream(dev)), "ofl_flow_global_match_x16")
+    del ft, ot, pack
     return out, prob, stats
 
 
@@ -99,10 +136,13 @@ def flow_global_match_grad(feat: torch.Tensor, other: torch.Tensor, flow_sign: f
 
 
 def global_match(feat: torch.Tensor, other: torch.Tensor, flow_sign: float = -1.0, want_prob: bool = False):
-    """(the vectors, fp32 [N,2,H,W]; the matching probability, fp32 [N,H,W], or None).  When autograd is recording and `feat` or `other`
-    requires a gradient, the call goes through `_autograd.GlobalMatchFn`; the probability never carries one."""
+    """(the vectors, fp32 [N,2,H,W]; the matching probability, fp32 [N,H,W], or None).  Two float32 tensors take ofl_matching.hip, two
+    float16 or two bfloat16 tensors ofl_matching_x16.hip.  When autograd is recording and `feat` or `other` requires a gradient, the call
+    goes through `_autograd.GlobalMatchFn`; the probability never carries one."""
+    check_features(feat, other)
     if _wants_grad(feat, other):
         from . import _autograd
         return _autograd.GlobalMatchFn.apply(feat, other, flow_sign, want_prob)
-    out, prob, _ = flow_global_match(feat, other, flow_sign, want_prob, False)
+    forward = flow_global_match_x16 if feat.dtype in X16 else flow_global_match
+    out, prob, _ = forward(feat, other, flow_sign, want_prob, False)
     return out, prob

@@ -51,7 +51,8 @@ _SYMBOLS = ("ofl_version", "ofl_set_option", "ofl_warp_bwd_f32", "ofl_splat_fwd_
             "ofl_flow_propagate_local_f32", "ofl_flow_propagate_local_grad_f32", "ofl_flow_local_match_f32",
             "ofl_flow_local_match_grad_f32",
             "ofl_flow_sequence_loss_workspace_bytes", "ofl_flow_sequence_loss_f64", "ofl_flow_sequence_loss_grad_f32",   # (_sequence_loss.py)
-            "ofl_flow_chain_f32")                                                                                 # (_chain.py)
+            "ofl_flow_chain_f32",                                                                                 # (_chain.py)
+            "ofl_flow_global_match_x16", "ofl_flow_global_match_x16_pack_bytes")                                  # (_matching.py)
 _lib = None
 _load_lock = threading.RLock()
 

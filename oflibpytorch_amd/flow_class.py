@@ -449,7 +449,8 @@ class Flow(object):
     @classmethod
     def from_matching(cls, feat, other, ref: str = None, mask=None, return_prob: bool = None):
         """The flow between two frames by global matching of their features, as in GMFlow, UniMatch and the matching heads of tracking
-        and stereo networks: `feat` and `other` are float32 tensors of one shape, C-H-W or N-C-H-W.  For every pixel p of `feat` the
+        and stereo networks: `feat` and `other` are float32 tensors of one shape, C-H-W or N-C-H-W -- or both float16 or both bfloat16,
+        as a network under autocast has them (below).  For every pixel p of `feat` the
         softmax over ALL positions q of `other` of feat(p) . other(q) / sqrt(C) gives the expected position of its match; the vector
         of an 's' flow at p is that position minus p, the vector of a 't' flow (the default `ref`) its negation, with the meaning the
         reference has in `Flow.corr_lookup`.  Returns a flow of shape N-H-W on the features' device with `mask` handed to the constructor
@@ -458,14 +459,21 @@ class Flow(object):
         pixels with a running maximum and three running float64 sums per pixel: the (H W)^2 volume is never formed and no logit is
         written to memory; every sum has a fixed order, bitwise reproducible and independent of the batch.
         Differentiable with respect to `feat` and `other`, by kernels that recompute the logits, without atomics;
-        NOT through the probability.  16-bit and channels_last features, a mask over the positions of `other`, a local window, another
-        temperature and the 1-D variant are not supported."""
+        NOT through the probability.  Two float16 or two bfloat16 tensors take ofl_matching_x16.hip: the logits are
+        formed on the matrix cores from the 16-bit values (products exact, float32 sums in the hardware's order), the weights are
+        float32 exponentials, summed in float32 inside a chunk of the walk and in float64 across chunks; the flow and the probability
+        are float32 as before and agree with the float64 evaluation within the bar DESIGN.md 4 derives, not bit for bit with the
+        float32 route; the gradients come from the float32 gradient kernels on transient up-conversions and are rounded once to the
+        features' dtype.  A mixed pair of dtypes, channels_last features, a mask over the positions of `other`, a local window,
+        another temperature and the 1-D variant are not supported."""
         err = "Error matching flow: "
         for name, ft in (("Feat", feat), ("Other", other)):
             if not isinstance(ft, torch.Tensor):
                 raise TypeError(err + name + " needs to be a torch tensor")
-            if ft.dtype != torch.float32:
-                raise TypeError(err + name + " needs to be of dtype float32")
+            if ft.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+                raise TypeError(err + name + " needs to be of dtype float32, float16 or bfloat16")
+        if feat.dtype != other.dtype:
+            raise TypeError(err + "Feat and other need to be both float32, both float16 or both bfloat16, not a mixed pair")
         return_prob = False if return_prob is None else return_prob
         if not isinstance(return_prob, bool):
             raise TypeError(err + "Return_prob needs to be boolean")

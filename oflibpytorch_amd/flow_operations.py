@@ -197,7 +197,8 @@ def global_matching_flow(feat, other, ref: str, return_prob: bool = None):
     """Flow.from_matching(feat, other, ref).vecs: the flow between two frames by global matching of their float32 features `feat` and
     `other` (C-H-W or N-C-H-W, one shape), GMFlow's softmax over all positions, float32 N-2-H-W (2-H-W for 3-D input), differentiable
     with respect to both tensors.  With `return_prob` True a tuple of the vectors and the matching probability, N-H-W (H-W for 3-D
-    input).  An extension: the reference has no such function."""
+    input).  Two float16 or two bfloat16 tensors are matched on the matrix cores: the vectors and the probability
+    stay float32, the gradients have the features' dtype.  An extension: the reference has no such function."""
     res = Flow.from_matching(feat, other, ref, return_prob=return_prob)
     flow, prob = res if isinstance(res, tuple) else (res, None)
     v = flow.vecs if feat.dim() > 3 else flow.vecs.squeeze(0)
